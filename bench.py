@@ -7,6 +7,10 @@ bf16 compute, feature encoder frozen, CTC reduction "mean", the train script's r
 forward -> CTC loss+grad -> backward -> [RCCL all-reduce] -> grad-norm clip + AdamW, on a synthetic batch that is
 already resident in HBM.  One process per GPU; for N > 1 launch under torch.distributed.run (weak scaling:
 the per-GPU batch is fixed).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line.  --full adds everything else this benchmark
+measures: the roofline survey and passes, the optimizer-tail stall, the long run, the batch sweep, the secondary workloads,
+the ingest path and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -165,11 +169,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32, help="utterances per GPU per step")
     ap.add_argument("--seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads (Whisper-small, XLSR-large bucketed, ingest)")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the per-GPU batch sweep (8, 16) and the un-folded normalisation run after the timed region")
-    ap.add_argument("--long-steps", type=int, default=100, help="extra untimed-by-the-driver run after the timed region (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="measure everything beside the headline too (roofline, optimizer tail, long run, "
+                    "batch sweep, secondary workloads, ingest, CPU baseline); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last timed step's loss and a fixed sample of "
+                    "the updated parameters and of their gradients as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads (Whisper-small, XLSR-large bucketed, ingest)")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the per-GPU batch sweep (8, 16) and the un-folded normalisation run after the timed region")
+    ap.add_argument("--long-steps", type=int, default=100, help="with --full: extra untimed-by-the-driver run after the timed region (0 = skip)")
     args = ap.parse_args()
+    full = args.full
     build = build_stamp()  # before anything touches the GPU: it spawns git (no child processes under a profiler's preload later)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -218,7 +227,7 @@ def main():
     sd["wav2vec2.encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
     model.load_state_dict(sd)
     opt = AdamW(model, lr=1e-4, weight_decay=0.0, max_grad_norm=1.0, warmup_steps=500, total_steps=100000)
-    trainer = Trainer(model, opt, measure_stall=True)
+    trainer = Trainer(model, opt, measure_stall=full)
     if os.environ.get("SSAK_TILE_ORDER") == "1":  # development switch: ticket tile order without a process group
         model.set_option(hip.W2V2_OPT_DYNAMIC_TILES, 1)
     if os.environ.get("SSAK_BENCH_POSCONV_GEMM") == "1":  # A/B switch: the positional convolution as the Toeplitz GEMM of rounds 1-2
@@ -268,8 +277,9 @@ def main():
             rows = [merged[r[0]] for r in rows] + [r for r in side if r[0] not in names]
         return rows
 
-    n_cold = 2 if args.warmup >= 5 else (1 if args.warmup >= 4 else 0)  # first launches load code objects, size workspaces, allocate copies
-    n_survey = min(2, args.warmup - n_cold)
+    # (a plain run brackets nothing: all of its warm-up steps are plain steps)
+    n_cold = (2 if args.warmup >= 5 else (1 if args.warmup >= 4 else 0)) if full else 0  # first launches load code objects, size workspaces, allocate copies
+    n_survey = min(2, args.warmup - n_cold) if full else 0
     for _ in range(n_cold):
         trainer.train_step(waves, None, labels)
     sync()
@@ -296,13 +306,15 @@ def main():
         dom_kernel = max(by_kernel, key=lambda k: sum(survey[i][2] for i in by_kernel[k]))
         dom_slots = by_kernel[dom_kernel]
         dom = max(dom_slots, key=lambda i: survey[i][2])
-    prof_enable(2 + dom if dom >= 0 else 1)
-    if os.environ.get("SSAK_BENCH_NO_PROF") == "1":  # development switch: cost of the events
-        prof_enable(0)
+    if full:
+        prof_enable(2 + dom if dom >= 0 else 1)
+        if os.environ.get("SSAK_BENCH_NO_PROF") == "1":  # development switch: cost of the events
+            prof_enable(0)
     for _ in range(args.warmup - n_cold - n_survey):
         trainer.train_step(waves, None, labels)
     sync()
-    prof_collect()  # (drops what the plain warm-up steps recorded for the dominant slot)
+    if full:
+        prof_collect()  # (drops what the plain warm-up steps recorded for the dominant slot)
     # no Python garbage collection inside the timed region: a generation-2 pass over the survey's objects stopped the host for
     # ~40 ms in the first timed step of every other run (SSAK_BENCH_STEP_TRACE=1: host issue 41.9 ms, device 57.1 ms for that step)
     import gc
@@ -327,18 +339,29 @@ def main():
         evs = [e for e, _ in trace] + [end]
         print("per-step device ms:", " ".join(f"{evs[i].elapsed_time(evs[i + 1]):.1f}" for i in range(len(trace))), file=sys.stderr)
         print("host issue ms:", " ".join(f"{(trace[i + 1][1] - trace[i][1]) * 1e3:.1f}" for i in range(len(trace) - 1)), file=sys.stderr)
-    prof_enable(0)
-    prof = prof_collect()
+    prof = []
+    if full:
+        prof_enable(0)
+        prof = prof_collect()
     kept_avg = (model.kept_layers - kl0) / max(1, model.train_forwards - fw0)
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax.item())
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        # before any further step: what the last timed step returned (its loss) and left in the model (the updated parameters
+        # and their gradients, 377 MB each for base: a fixed seeded sample of the trainable ones)
+        n = model.num_trainable
+        idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, 1 << 20), replace=False))
+        idx = torch.from_numpy(idx).to(dev)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("loss", loss), ("params_sample", model.params[idx]), ("grads_sample", model.grads[idx])):
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), t.detach().float().cpu().numpy().reshape(-1))
     # exposed part of the exchange + optimizer tail (side stream): how long a forward waits for the previous update, sampled
     # on a few extra untimed steps (reading the events synchronises)
     stalls = []
-    for _ in range(3):
+    for _ in range(3 if full else 0):
         trainer.train_step(waves, None, labels)
         trainer.train_step(waves, None, labels)
         stalls.append(trainer.stall_ms())
@@ -360,7 +383,7 @@ def main():
     # a longer run of the same step after the driver's timed region (profiler markers off): box noise and LayerDrop's
     # step-to-step work differences average out over it
     long_run = None
-    if args.long_steps > 0:
+    if full and args.long_steps > 0:
         prof_enable(0)
         t1 = time.perf_counter()
         for _ in range(args.long_steps):
@@ -377,7 +400,7 @@ def main():
     # "per-GPU batch B in {8, 16, 32}; report best" -- the other batch sizes through the same model / trainer,
     # a short timed run each (the reference's default is --batch_size 8, wav2vec_train.py:158); the headline stays the --batch line
     sweep = []
-    if world == 1 and not args.no_sweep and not args.no_secondary:  # (profiler passes run --no-secondary: only the headline's launches)
+    if world == 1 and full and not args.no_sweep and not args.no_secondary:  # (profiler passes run --no-secondary: only the headline's launches)
         for Bs in (8, 16):
             if Bs == B:
                 continue
@@ -417,7 +440,7 @@ def main():
         utts = B * world * args.steps
         value = utts / dt
 
-        attn_valu = attention_valu_per_element(build, float(B) * cfg.num_attention_heads * model.num_frames(T) ** 2)
+        attn_valu = attention_valu_per_element(build, float(B) * cfg.num_attention_heads * model.num_frames(T) ** 2) if full else None
 
         def entry(p, steps):
             name, launches, ms, work, bound = p
@@ -498,28 +521,30 @@ def main():
                "unit": "utterances/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
                "vs_baseline": None, "dtype": "bf16", "data": "synthetic, HBM-resident batch (the timed loop re-feeds one device batch; the "
-               "file -> device path is measured beside it: ingest)",
+               "file -> device path is measured beside it with --full: ingest)",
                "config": {"workload": "Wav2Vec2-base CTC fine-tune step, bf16, synthetic 10 s @16 kHz utterances "
                                       "(BASELINE.json configs[1]; DP over xGMI for n_gpus>1 = configs[2])",
                           "per_gpu_batch": B, "global_batch": B * world, "samples_per_utt": T, "frames": model.num_frames(T),
                           "frozen_feature_encoder": True, "regularisers": "script defaults (dropout/layerdrop/specaugment on)",
                           "parallelism": f"dp{world}", "final_loss": round(final_loss, 4),
                           "kept_layers_per_step": round(kept_avg, 3)},
-               "roofline": roof, "build": build,
-               "optimizer_tail": {"stream": "side" if trainer.opt_stream is not None else "compute",
-                                  "exposed_us_per_step": None if np.isnan(np.median(stalls)) else round(1e3 * float(np.median(stalls)), 1),
-                                  "bucket_wait_us": trainer.bucket_wait_us(),
-                                  "note": "exposed_us_per_step: wait of the forward at its first trainable-parameter read (after the frozen "
-                                          "conv stack) for the exchange tail + clip + AdamW of the previous step; bucket_wait_us: per "
-                                          "gradient bucket (announcement order), time the optimizer stream sat at its all-reduce "
-                                          "(null without a process group)"}}
+               "build": build}
+        if full:
+            out["roofline"] = roof
+            out["optimizer_tail"] = {"stream": "side" if trainer.opt_stream is not None else "compute",
+                                     "exposed_us_per_step": None if np.isnan(np.median(stalls)) else round(1e3 * float(np.median(stalls)), 1),
+                                     "bucket_wait_us": trainer.bucket_wait_us(),
+                                     "note": "exposed_us_per_step: wait of the forward at its first trainable-parameter read (after the frozen "
+                                             "conv stack) for the exchange tail + clip + AdamW of the previous step; bucket_wait_us: per "
+                                             "gradient bucket (announcement order), time the optimizer stream sat at its all-reduce "
+                                             "(null without a process group)"}
+            out["long_run"] = long_run
         if world > 1:
             out["exchange"] = {"backend": backend, "rccl_ranks": world, "collective": "sum all-reduce per gradient bucket, "
                                "issued from the engine's grad-ready callback while the backward runs",
                                "grad_dtype": trainer.grad_exchange_dtype,
                                "bucket_bytes": [c * (2 if trainer.grad_exchange_dtype == "bf16" else 4) for _, c in trainer.bucket_log],
                                "payload_bytes_per_step": sum(c for _, c in trainer.bucket_log) * (2 if trainer.grad_exchange_dtype == "bf16" else 4)}
-        out["long_run"] = long_run
         if sweep:
             tf_h = gf_per_utt(kept_avg) * 1e9 * B * args.steps / dt / 1e12
             rows = sorted(sweep + [{"per_gpu_batch": B, "value": round(value, 2), "ms_per_step": round(dt / args.steps * 1e3, 3), "steps": args.steps,
@@ -531,7 +556,7 @@ def main():
                                     "note": "the headline batch is un-padded (every utterance fills T), so ssak_amd.train and this bench fold the waveform "
                                             "normalisation (a1) into conv0's GroupNorm statistics; padded / ragged batches and the layer-norm topology run "
                                             "ssak_wave_normalize as a pass of its own (both figures: three alternating blocks of ten steps each, after the timed region)"}
-        if world == 1 and not args.no_secondary:
+        if world == 1 and full and not args.no_secondary:
             # BASELINE.json configs[3] / configs[4] and the ingest path on the same clock as the headline (their models are built after
             # the headline's timed region; its buffers are released first)
             del trainer, opt, model
@@ -568,7 +593,7 @@ def main():
                 out["online"]["vs_resident_batch"] = round(out["online"]["value"] / value, 4)
             except Exception as e:
                 out["online"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -19,14 +19,19 @@ from typing import List, Sequence
 import numpy as np
 
 
-def get_trellis(emission: np.ndarray, tokens: Sequence[int], blank_id: int = 0, first_as_garbage: bool = False) -> np.ndarray:
-    """emission [F, V] float32 log-probabilities -> trellis [F+1, L+1] float32 (align_transcriptions.py:27-70)."""
+def get_trellis(emission: np.ndarray, tokens: Sequence[int], blank_id: int = 0, first_as_garbage: bool = False,
+                column0: np.ndarray | None = None) -> np.ndarray:
+    """emission [F, V] float32 log-probabilities -> trellis [F+1, L+1] float32 (align_transcriptions.py:27-70).
+    ``column0``: trellis[1:, 0] as given instead of computed (tests replay the recurrence from a golden's column 0: the garbage
+    variant's torch log can differ in the last ulp from host to host)."""
     emission = np.asarray(emission, dtype=np.float32)
     tokens = np.asarray(tokens, dtype=np.int64)
     F, L = emission.shape[0], len(tokens)
     trellis = np.empty((F + 1, L + 1), dtype=np.float32)
     trellis[0, 0] = 0
-    if first_as_garbage:
+    if column0 is not None:
+        trellis[1:, 0] = column0
+    elif first_as_garbage:
         import torch  # the reference's own float32 exp / log (numpy's differ in the last ulp)
         trellis[1:, 0] = (1 - torch.from_numpy(np.ascontiguousarray(emission[:, tokens[0]])).exp()).log().numpy()  # :38
     else:

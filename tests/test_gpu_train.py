@@ -688,7 +688,7 @@ def test_bench_two_rank_rehearsal_reports_the_exchange(tmp_path):
         port = s.getsockname()[1]
     env = dict(os.environ, PYTHONPATH=ROOT, SSAK_BENCH_SHARE_GPU="1", SSAK_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "3",
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "3",
                         "--batch", "4"], env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -700,6 +700,30 @@ def test_bench_two_rank_rehearsal_reports_the_exchange(tmp_path):
     waits = tail["bucket_wait_us"]
     assert waits is not None and len(waits) == len(ex["bucket_bytes"]) and all(w >= 0 for w in waits)
     assert d["roofline"]["primary"]["frac"] > 0 and d["build"]["lib_sha256"]
+
+
+def test_bench_plain_line_and_dumped_outputs_repeat(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps and prints the headline line without the side legs;
+    --dump-outputs writes the last timed step's loss and parameter / gradient samples as float32 .npy files, and a second run
+    with the same arguments writes the same arrays bit for bit."""
+    def run(out):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "2",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+
+    d = run(tmp_path / "a")
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "utterances/sec" and d["dtype"] == "bf16"
+    assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) <= 0.01 * d["value"] and d["higher_is_better"] is True
+    assert not {"roofline", "optimizer_tail", "long_run", "headline_sweep", "secondary", "ingest", "online", "cpu_baseline"} & set(d)
+    run(tmp_path / "b")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["grads_sample.npy", "loss.npy", "params_sample.npy"] and names == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), n
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")[0]) - d["config"]["final_loss"]) < 1e-3 * abs(d["config"]["final_loss"]) + 1e-4
 
 
 def test_train_step_is_bitwise_reproducible():

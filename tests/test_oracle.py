@@ -168,8 +168,20 @@ def test_align_oracle_vs_torch_golden(gold, name):
     from oracle import align_ref
     z = gold("align.npz")
     em, tok, blank = z[f"{name}_emission"], z[f"{name}_tokens"].tolist(), int(z[f"{name}_blank"])
-    tr = align_ref.get_trellis(em, tok, blank, bool(z[f"{name}_garbage"]))
-    assert np.array_equal(tr, z[f"{name}_trellis"])
+    garbage, want = bool(z[f"{name}_garbage"]), z[f"{name}_trellis"]
+    tr = align_ref.get_trellis(em, tok, blank, garbage)
+    if garbage:
+        # column 0 is the reference's float32 torch expression log(1 - exp(x)); torch's CPU log can differ in the last ulp from
+        # the host that wrote the golden (measured: an AMD EPYC host, every ATEN_CPU_CAPABILITY).  Where it does, the oracle
+        # must still equal that expression on THIS host bit for bit, the golden must be within one ulp of it, and the recurrence
+        # and backtrack from the golden's column 0 must reproduce the golden bit for bit.
+        rows = len(em) - len(tok)  # (the last L rows of column 0 are +inf)
+        host = (1 - torch.from_numpy(np.ascontiguousarray(em[:, tok[0]])).exp()).log().numpy()[:rows]
+        assert np.array_equal(tr[1:rows + 1, 0], host)
+        if not np.array_equal(host, want[1:rows + 1, 0]):
+            assert np.abs(host.view(np.int32) - want[1:rows + 1, 0].view(np.int32)).max() <= 1
+            tr = align_ref.get_trellis(em, tok, blank, garbage, column0=want[1:, 0])
+    assert np.array_equal(tr, want)
     if not int(z[f"{name}_ok"]):
         with pytest.raises(RuntimeError):
             align_ref.backtrack(tr, em, tok, blank)

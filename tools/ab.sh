@@ -12,8 +12,8 @@ d=json.loads(sys.stdin.read()); r=d["roofline"]; lr=d.get("long_run") or {}
 print("%-12s %8.1f %7.3f | long %8.1f %7.3f | %s" % (sys.argv[1], d["value"], d["ms_per_step"], lr.get("value", 0), lr.get("ms_per_step", 0),
       " | ".join("%s %.0f" % (k["kernel"].replace("gemm_", "").replace("_kernel", "")[:34], k["us_per_step"]) for k in r["kernels"][:12] if "gemm" in k["kernel"] or "attn" in k["kernel"])))'
 for i in $(seq $N); do
-  python bench.py --steps 20 --warmup 5 --long-steps 100 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "$show" "ship"
+  python bench.py --full --steps 20 --warmup 5 --long-steps 100 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "$show" "ship"
   for lib in "$@"; do
-    SSAK_HIP_LIB=$PWD/${lib#$PWD/} python bench.py --steps 20 --warmup 5 --long-steps 100 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "$show" "$(basename $lib .so)"
+    SSAK_HIP_LIB=$PWD/${lib#$PWD/} python bench.py --full --steps 20 --warmup 5 --long-steps 100 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "$show" "$(basename $lib .so)"
   done
 done

@@ -11,6 +11,6 @@ print("%-40s %8.1f %7.3f | long %8.1f %7.3f | optimizer tail exposed %s us" % (s
       (d.get("optimizer_tail") or {}).get("exposed_us_per_step")))'
 for i in $(seq $N); do
   for set in "$@"; do
-    env $set python bench.py --steps 20 --warmup 5 --long-steps 100 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "$show" "$set"
+    env $set python bench.py --full --steps 20 --warmup 5 --long-steps 100 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "$show" "$set"
   done
 done

@@ -11,9 +11,10 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out profiles
 rm -rf gpurun_out/prof_${R} gpurun_out/pmc_fetch gpurun_out/pmc_write gpurun_out/pmc_sq
 python3 tools/stamp.py show > gpurun_out/${R}_stamp_before.json
-# 1. the plain bench line (no profiler attached): what the driver will measure
-python3 bench.py --batch 32 --steps 100 --warmup 5 > gpurun_out/${R}_bench_b32.json 2> gpurun_out/${R}_bench_b32.err
-echo "bench done: $(python3 -c "import json;d=json.load(open('gpurun_out/${R}_bench_b32.json'));print(d['value'], d['ms_per_step'])")"
+LINES=$(mktemp -d)  # the two bench lines, merged into profiles/${R}_bench_b32.json below
+# 1. the bench line with all of its legs (no profiler attached): the headline the driver will measure, roofline, side workloads
+python3 bench.py --full --batch 32 --steps 100 --warmup 5 > $LINES/a.json
+echo "bench done: $(python3 -c "import json;d=json.load(open('$LINES/a.json'));print(d['value'], d['ms_per_step'])")"
 CMD="python3 $ROOT/bench.py --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --long-steps 0"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/gpurun_out/prof_${R} -- python3 $ROOT/bench.py --batch 32 --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --long-steps 0 > $ROOT/gpurun_out/prof_${R}_bench.json 2> $ROOT/gpurun_out/prof_${R}.err
@@ -40,15 +41,15 @@ cp $(ls -t gpurun_out/prof_${R}_logmel/*/*kernel_stats.csv | head -1) profiles/$
 grep log-mel gpurun_out/${R}_logmel.log > profiles/${R}_logmel.log
 cp gpurun_out/${R}_vendor_gemm.log profiles/${R}_vendor_gemm.log
 cp gpurun_out/prof_${R}_bench.json profiles/${R}_bench_b32_under_rocprof.json
-cp gpurun_out/${R}_bench_b32.json profiles/${R}_bench_b32.json
+cp $LINES/a.json profiles/${R}_bench_b32.json
 # second bench line AFTER the traffic file exists: its roofline.traffic is read from this round's (same-library) passes
-python3 bench.py --batch 32 --steps 100 --warmup 5 --no-cpu-baseline --no-secondary > gpurun_out/${R}_bench_b32_b.json 2>> gpurun_out/${R}_bench_b32.err
+python3 bench.py --full --batch 32 --steps 100 --warmup 5 --no-cpu-baseline --no-secondary > $LINES/b.json
 python3 - <<PY
 import hashlib, json, sys
 sys.path.insert(0, "tools")
 import stamp
 R = "${R}"
-a, b = json.load(open(f"gpurun_out/{R}_bench_b32.json")), json.load(open(f"gpurun_out/{R}_bench_b32_b.json"))
+a, b = json.load(open("$LINES/a.json")), json.load(open("$LINES/b.json"))
 # the committed line is the SECOND run (its roofline.traffic comes from this round's passes) with the cpu_baseline leg of the
 # first; both throughputs are listed (same build, same box, minutes apart) -- no picking
 best = dict(b, **{k: v for k, v in a.items() if k not in b})  # every side leg of the first run (cpu_baseline, secondary, ingest, online ...)

@@ -1,5 +1,5 @@
 """Development aid: print the headline figures and the per-kernel survey of one bench.py JSON line.
-usage: python tools/show_bench.py gpurun_out/check_bench.json"""
+usage: python tools/show_bench.py LINE.json  (one line of bench.py --full)"""
 import json
 import sys
 
