@@ -111,6 +111,56 @@ size_t ssak_ctc_wer_workspace_bytes(int B, int F, int Lmax);
 int ssak_ctc_wer(const int32_t* hyp_ids, const int32_t* hyp_lens, const int32_t* labels, const uint8_t* token_class, int B, int F,
                  int Lmax, int V, int32_t* edits, int32_t* ref_words, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- f4: CTC beam search with an ARPA n-gram LM ------------------------------------------------
+ * Replaces the --arpa path of ssak/infer/transformers_infer.py:97-133 (pyctcdecode + KenLM, transformers_decoder_with_lm
+ * :272-295) under a contract of its own, modelled on pyctcdecode's defaults; pyctcdecode parity unpinned.  The contract
+ * (scores, merges, tie rule, LM terms) is written out in ssak_amd/lm.py.  The LM tables are built by that module from an
+ * ARPA text file: a unigram trie over LABEL ids as an open-addressing hash (node, label) -> child (root = node 0),
+ * unigram (log10 p, log10 backoff) pairs by word id, and one open-addressing hash per order >= 2 keyed by the full word-id
+ * tuple.  Hashes: lm_hash of ssak_amd/lm.py (FNV-1a over the int32 ids + a finaliser), linear probing, every probe loop
+ * bounded by the table size.  All pointers in the descriptors are device pointers. */
+#define SSAK_LM_MAX_ORDER 6
+#define SSAK_LM_MAX_BEAM 256
+#define SSAK_LM_MAX_LABELS 1024
+typedef struct {
+  int order;                  /* 1..SSAK_LM_MAX_ORDER */
+  int n_words;                /* word ids 0..n_words-1 */
+  int bos, eos, unk;          /* word ids of <s>, </s>, <unk> */
+  int trie_cap;               /* power of two */
+  int n_nodes;                /* trie nodes (node_word entries) */
+  const int32_t* trie;        /* [trie_cap][3] (node, label, child); node -1 = empty slot */
+  const int32_t* node_word;   /* [n_nodes] word id spelled by the path to the node, or -1 */
+  const float* uni;           /* [n_words][2] (log10 p, log10 backoff) */
+  const int32_t* ng_keys[SSAK_LM_MAX_ORDER]; /* [k-1] for order k >= 2: [ng_cap[k-1]][k] word ids; first id -1 = empty */
+  const float* ng_val[SSAK_LM_MAX_ORDER];    /* [k-1]: [ng_cap[k-1]][2] (log10 p, log10 backoff) */
+  int ng_cap[SSAK_LM_MAX_ORDER];             /* powers of two */
+} ssak_ngram_lm;
+
+typedef struct {
+  int beam_width;             /* 1..SSAK_LM_MAX_BEAM */
+  int n_labels;               /* columns of the logits that are labels (len(tokenizer)): 1..min(V, SSAK_LM_MAX_LABELS) */
+  int blank;                  /* CTC blank (pad) id, < n_labels */
+  const uint8_t* label_class; /* device [n_labels]: 0 character, 1 word delimiter, 2 label without text */
+  float alpha, beta;          /* LM weight, word insertion bonus */
+  float beam_prune_logp;      /* candidates below best + this are dropped (-INFINITY: off) */
+  float token_min_logp;       /* tokens below this log-probability are not tried (the frame's argmax always is) */
+  float unk_score_offset;     /* log10 penalty of an OOV word / prefix */
+} ssak_lm_beam_params;
+
+/* logits [B, F, V] fp32 raw; in_lens [B] valid frames (NULL = F).  ids [B, F] int32: the winner's label ids left-aligned,
+ * -1 beyond; n [B] their counts (-1: the utterance's prefix store overflowed, which the workspace size rules out);
+ * score [B] fp32: the winner's total.  One workgroup per utterance; bit-reproducible, and an utterance's result does not
+ * depend on the rest of the batch.  workspace >= ssak_ctc_lm_beam_workspace_bytes(B, F, V, beam_width). */
+size_t ssak_ctc_lm_beam_workspace_bytes(int B, int F, int V, int beam_width);
+int ssak_ctc_lm_beam_decode(const float* logits, const int32_t* in_lens, int B, int F, int V, const ssak_ngram_lm* lm /*host*/,
+                            const ssak_lm_beam_params* params /*host*/, int32_t* ids, int32_t* n, float* score,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* Batched n-gram lookup (tests compare the device tables with the host's): log10p[q] = log10 P(words[q] | ctx) with ARPA
+ * backoff, ctx = ctx_ids[q][0 .. order-2] (most recent last; only the trailing run of ids >= 0 is used); NaN when an id is
+ * out of range. */
+int ssak_lm_query(const ssak_ngram_lm* lm /*host*/, const int32_t* ctx_ids, const int32_t* words, int Q, float* log10p,
+                  void* stream);
+
 /* ---- f1: CTC forced alignment (Viterbi trellis + backtrack) ----------------------------------
  * Replaces get_trellis + backtrack of ssak/utils/align_transcriptions.py:27-70,79-123 (USE_MAX, USE_CHAR_REPEATED),
  * reached from compute_alignment (:294-402) under tools/align_audio_transcript.py:121,335.

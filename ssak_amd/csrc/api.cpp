@@ -18,7 +18,7 @@ void ssak_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int ssak_version(void) { return 510; }  // round 6: ssak_drop_file_cache, plan_tile 129 gone, conv0 statistics as (mean, rstd) (INTEGRATION.md "ABI 510")
+extern "C" int ssak_version(void) { return 520; }  // ssak_ngram_lm / ssak_lm_beam_params, ssak_ctc_lm_beam_decode, ssak_lm_query (INTEGRATION.md "ABI 520")
 extern "C" const char* ssak_last_error(void) { return g_err; }
 
 // ---- optional per-launch timing (bench.py's roofline leg): HIP events around launches, on the launch's own stream ----

@@ -13,7 +13,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 510  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 520  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -43,6 +43,18 @@ class ProfEntry(C.Structure):
                 ("bound", C.c_int)]
 
 
+class NgramLMDesc(C.Structure):  # ssak_ngram_lm
+    _fields_ = [("order", C.c_int), ("n_words", C.c_int), ("bos", C.c_int), ("eos", C.c_int), ("unk", C.c_int),
+                ("trie_cap", C.c_int), ("n_nodes", C.c_int), ("trie", C.c_void_p), ("node_word", C.c_void_p), ("uni", C.c_void_p),
+                ("ng_keys", C.c_void_p * 6), ("ng_val", C.c_void_p * 6), ("ng_cap", C.c_int * 6)]
+
+
+class LMBeamParams(C.Structure):  # ssak_lm_beam_params
+    _fields_ = [("beam_width", C.c_int), ("n_labels", C.c_int), ("blank", C.c_int), ("label_class", C.c_void_p),
+                ("alpha", C.c_float), ("beta", C.c_float), ("beam_prune_logp", C.c_float), ("token_min_logp", C.c_float),
+                ("unk_score_offset", C.c_float)]
+
+
 GRAD_READY_FN = C.CFUNCTYPE(None, C.c_long, C.c_long, C.c_void_p)
 
 
@@ -64,6 +76,10 @@ def _load():
         "ssak_ctc_workspace_bytes": (sz, [i32, i32, i32, i32]),
         "ssak_ctc_loss_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, sz, vp]),
         "ssak_ctc_greedy_decode": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "ssak_ctc_lm_beam_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "ssak_ctc_lm_beam_decode": (i32, [vp, vp, i32, i32, i32, C.POINTER(NgramLMDesc), C.POINTER(LMBeamParams), vp, vp, vp,
+                                          vp, sz, vp]),
+        "ssak_lm_query": (i32, [C.POINTER(NgramLMDesc), vp, vp, i32, vp, vp]),
         "ssak_read_ranges": (i32, [vp, vp, vp, vp, i32, i32]),
         "ssak_drop_file_cache": (i32, [vp, i32]),
         "ssak_pcm_to_mono_f32": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
@@ -251,6 +267,34 @@ def ctc_greedy_decode(logits: torch.Tensor, in_lens: torch.Tensor | None = None,
     n = torch.empty(B, dtype=torch.int32, device=logits.device)
     check(lib.ssak_ctc_greedy_decode(ptr(logits), ptr(in_lens), B, F, V, blank, ptr(ids), ptr(n), stream()))
     return ids, n
+
+
+def ctc_lm_beam_decode(logits: torch.Tensor, in_lens: torch.Tensor | None, lm: NgramLMDesc, *, n_labels: int, blank: int,
+                       label_class: torch.Tensor, alpha: float, beta: float, beam_width: int, beam_prune_logp: float,
+                       token_min_logp: float, unk_score_offset: float, workspace: torch.Tensor | None = None):
+    """CTC beam search with an n-gram LM (``ssak_ctc_lm_beam_decode``; contract: ssak_amd/lm.py) -> (ids [B,F], n [B], score [B])."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3 and logits.is_contiguous()
+    B, F, V = logits.shape
+    if in_lens is not None:
+        in_lens = in_lens.to(device=logits.device, dtype=torch.int32).contiguous()
+    p = LMBeamParams(int(beam_width), int(n_labels), int(blank), label_class.data_ptr(), float(alpha), float(beta),
+                     float(beam_prune_logp), float(token_min_logp), float(unk_score_offset))
+    ids = torch.empty((B, F), dtype=torch.int32, device=logits.device)
+    n = torch.empty(B, dtype=torch.int32, device=logits.device)
+    score = torch.empty(B, dtype=torch.float32, device=logits.device)
+    ws = workspace if workspace is not None else _ws(lib.ssak_ctc_lm_beam_workspace_bytes(B, F, V, int(beam_width)), logits.device)
+    check(lib.ssak_ctc_lm_beam_decode(ptr(logits), ptr(in_lens), B, F, V, C.byref(lm), C.byref(p), ptr(ids), ptr(n), ptr(score),
+                                      ptr(ws), ws.numel(), stream()))
+    return ids, n, score
+
+
+def lm_query(lm: NgramLMDesc, ctx_ids: torch.Tensor, words: torch.Tensor):
+    """log10 P(words[q] | ctx_ids[q]) with ARPA backoff (``ssak_lm_query``); ctx_ids [Q, order-1] int32, most recent last."""
+    words = words.to(dtype=torch.int32).contiguous()
+    ctx_ids = ctx_ids.to(device=words.device, dtype=torch.int32).contiguous()
+    out = torch.empty(words.numel(), dtype=torch.float32, device=words.device)
+    check(lib.ssak_lm_query(C.byref(lm), ptr(ctx_ids), ptr(words), words.numel(), ptr(out), stream()))
+    return out
 
 
 def ctc_wer(hyp_ids: torch.Tensor, hyp_lens: torch.Tensor, labels: torch.Tensor, token_class: torch.Tensor):

@@ -1,6 +1,8 @@
 """Inference entry point: the counterpart of ``ssak/infer/transformers_infer.py`` (console script ``sak_infer``)
 with the acoustic model on HIP kernels.  Same functions, arguments and CLI flags
-(transformers_infer.py:14-133,190-269,316-365); ``--arpa`` (KenLM beam search on the CPU) is outside this path.
+(transformers_infer.py:14-133,190-269,316-365).  Without ``--arpa`` the decode is greedy (argmax + collapse on the device);
+with ``--arpa`` it is a CTC beam search with the ARPA n-gram LM on the device (ssak_amd/lm.py: a contract modelled on
+pyctcdecode's defaults with the reference's alpha / beta, pyctcdecode parity unpinned; KenLM binary LMs are not read).
 """
 from __future__ import annotations
 
@@ -68,10 +70,13 @@ def compute_log_probas(model_and_processor, audio: np.ndarray, sample_rate: int 
 def transformers_infer(source, audios, batch_size: int = 1, device=None, language=None, arpa_path=None,
                        alpha: float = 0.5, beta: float = 1.0, sort_by_len: bool = False, output_ids: bool = False,
                        log_memtime: bool = False):
-    """Generator of transcripts (or (id, transcript)) -- greedy CTC path of transformers_infer.py:73-95."""
-    if arpa_path is not None:
-        raise NotImplementedError("--arpa: n-gram LM beam search (pyctcdecode/kenlm, CPU) is outside the HIP path")
+    """Generator of transcripts (or (id, transcript)) -- greedy CTC path of transformers_infer.py:73-95, or with ``arpa_path``
+    the LM beam search of :97-133 (ssak_amd.lm; ``alpha`` / ``beta`` weigh the LM).  The LM is loaded once per call."""
     model, tok = transformers_load_model(source, device)
+    lm = None
+    if arpa_path is not None:
+        from . import lm as lm_mod
+        lm = lm_mod.load_arpa(arpa_path, tok, model.device)
     for batch in to_audio_batches(audios, batch_size=batch_size, sort_by_len=sort_by_len, output_ids=output_ids):
         ids = None
         if output_ids:
@@ -81,7 +86,10 @@ def transformers_infer(source, audios, batch_size: int = 1, device=None, languag
         # argmax + collapse on the device (a12); only the short id strings cross PCIe
         lens = torch.tensor([model.num_frames(len(a)) for a in batch], dtype=torch.int32)
         with torch.cuda.device(model.device):
-            dec, n = hip.ctc_greedy_decode(logits, lens, tok.pad_token_id)
+            if lm is None:
+                dec, n = hip.ctc_greedy_decode(logits, lens, tok.pad_token_id)
+            else:
+                dec, n, _ = lm_mod.decode(logits, lens, lm, tok, alpha=alpha, beta=beta)
         dec, n = dec.cpu().numpy(), n.cpu().numpy()
         for i in range(len(batch)):
             text = tok.decode(dec[i, :n[i]], group_tokens=False)

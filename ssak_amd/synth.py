@@ -76,3 +76,52 @@ def write_kaldi_folder(folder: str, n_utts: int, seconds: float = 10.0, seed: in
             ft.write(f"utt{i:05d} {text}\n")
             fd.write(f"utt{i:05d} {seconds:.3f}\n")
     return rows
+
+
+def synth_words(rng: np.random.Generator, n: int, lo: int = 2, hi: int = 9):
+    """``n`` distinct seeded random words over a-z (lengths uniform in [lo, hi])."""
+    out, seen = [], set()
+    letters = np.array([chr(ord("a") + i) for i in range(26)])
+    while len(out) < n:
+        for L in rng.integers(lo, hi + 1, 2 * (n - len(out)) + 16):
+            w = "".join(letters[rng.integers(0, 26, L)])
+            if w not in seen:
+                seen.add(w)
+                out.append(w)
+                if len(out) == n:
+                    break
+    return out
+
+
+def write_arpa(path: str, words, counts, seed: int = 0):
+    """A seeded synthetic ARPA LM over ``words`` (plus <s>, </s>, <unk>): counts[k-1] distinct k-grams for k >= 2, each a
+    (k-1)-gram of the file extended by a random word; random log10 probabilities in [-4, -0.1] and backoffs in [-1, 0]
+    (the highest order has none).  Not a normalised distribution: it exercises the file format and the lookups."""
+    rng = np.random.default_rng(seed)
+    vocab = ["<s>", "</s>", "<unk>"] + list(words)
+    order = len(counts) + 1
+    grams = [np.arange(len(vocab), dtype=np.int64)[:, None]]
+    for k in range(2, order + 1):
+        prev = grams[-1]
+        want = counts[k - 2]
+        rows = np.zeros((0, k), dtype=np.int64)
+        while len(rows) < want:
+            m = 2 * (want - len(rows)) + 16
+            cand = np.concatenate([prev[rng.integers(0, len(prev), m)], rng.integers(1, len(vocab), (m, 1))], axis=1)
+            cand = cand[cand[:, 1:].min(axis=1) != 0]  # <s> only first
+            rows = np.unique(np.concatenate([rows, cand]), axis=0)
+        grams.append(rows[rng.permutation(len(rows))[:want]])
+    with open(path, "w") as f:
+        f.write("\\data\\\n" + "".join(f"ngram {k + 1}={len(g)}\n" for k, g in enumerate(grams)) + "\n")
+        for k, g in enumerate(grams):
+            f.write(f"\\{k + 1}-grams:\n")
+            p = rng.uniform(-4.0, -0.1, len(g))
+            bo = rng.uniform(-1.0, 0.0, len(g))
+            if k == 0:
+                p[0] = -99.0
+            last = k + 1 == order
+            f.write("".join(f"{p[i]:.4f}\t{' '.join(vocab[j] for j in g[i])}" + ("" if last or (k == 0 and g[i, 0] == 1) else f"\t{bo[i]:.4f}")
+                            + "\n" for i in range(len(g))))
+            f.write("\n")
+        f.write("\\end\\\n")
+    return vocab
