@@ -548,6 +548,62 @@ int ssak_cast_bf16_f32(const void* src_bf16, float* dst, long n, void* stream);
 size_t ssak_colsum_workspace_bytes(int N);
 int ssak_colsum_bf16(const void* X, long ld, int M, int N, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- augmentation (ABI 530): train --data_augment, the reference's SpeechAugment (ssak/utils/augment.py:123-180) -------
+ * Contract and draws: ssak_amd/augment.py.  Every parameter is drawn on the host and passed as one fp64 row of SSAK_AUG_NCOL
+ * columns per utterance, twice: `params` on the device (read by the kernels) and `params_host`, the same table in host
+ * memory (argument validation and launch sizing before any launch).  `lens` / `lens_host` likewise (samples, <= T).
+ * Results depend on an utterance's own row and samples only (fixed-order fp64 sums, per-utterance FFT sizes, no atomics). */
+#define SSAK_AUG_NONE (-1)
+#define SSAK_AUG_GAIN 0      /* y = x * gain_lin                                                          */
+#define SSAK_AUG_NOISE_MIX 1 /* y = x + n * (rms(x) / snr_amp) / rms(n), n = the tiled noise segment       */
+#define SSAK_AUG_REVERB 2    /* circular convolution with the RIR rotated by its peak, mean|.| rescaled    */
+#define SSAK_AUG_KIND 0
+#define SSAK_AUG_GAIN_DB 1
+#define SSAK_AUG_GAIN_LIN 2    /* 10^(gain_db / 20), computed on the host                                 */
+#define SSAK_AUG_SNR_DB 3
+#define SSAK_AUG_SNR_AMP 4     /* 10^(snr_db / 20), computed on the host                                  */
+#define SSAK_AUG_NOISE 5       /* noise bank entry                                                        */
+#define SSAK_AUG_NOISE_START 6 /* first sample of the segment in that entry                               */
+#define SSAK_AUG_RIR 7         /* RIR bank entry                                                          */
+#define SSAK_AUG_RIR_PEAK 8    /* argmax |h| over the full RIR (first maximum)                            */
+#define SSAK_AUG_RATE 9        /* time-stretch rate, [0.5, 2]                                             */
+#define SSAK_AUG_OUT_LEN 10    /* round(L / rate) (informative: the device recomputes it)                 */
+#define SSAK_AUG_NCOL 11
+/* A bank of 1-D fp32 signals (noise files, RIRs) resident on the device: entry i is data[offset[i] .. offset[i] + length[i]).
+ * offset / length in device memory, their host mirrors for validation. */
+typedef struct ssak_audio_bank {
+  int n;
+  const float* data;
+  const int64_t* offset;
+  const int32_t* length;
+  const int64_t* offset_host; /* host */
+  const int32_t* length_host; /* host */
+} ssak_audio_bank;
+/* Gain and background noise (rows of kind GAIN / NOISE_MIX; every other row is copied).  x and y [B, T] fp32, may alias.
+ * Noise: the segment is entry[start : start + min(L, N)], tiled up to L; rms(n) over the segment before tiling; rms(n) < 1e-9
+ * leaves y = x.  Samples past lens[b] are copied. */
+size_t ssak_augment_gain_noise_workspace_bytes(int B, int T);
+int ssak_augment_gain_noise(const float* x, const int32_t* lens, const int32_t* lens_host /*host*/, int B, int T, const double* params,
+                            const double* params_host /*host*/, const ssak_audio_bank* noise /*host struct; may be NULL without NOISE rows*/,
+                            float* y, void* workspace, size_t workspace_bytes, void* stream);
+/* Reverberation (rows of kind REVERB; every other row is copied).  augment_reverberation.py:104-177: h truncated to its first
+ * L samples, rotated by its peak d (d >= L: not rotated), circular convolution of length L, then
+ * y = w / (mean|w| + 1e-14) * mean|x|.  Computed as a linear convolution through one complex FFT of x + i h of
+ * N = 2^k >= L + min(Lh, L) - 1 points (four-step, N <= 2^24), folded modulo L.  x and y may alias.
+ * workspace >= ssak_augment_reverb_workspace_bytes(B, T, longest RIR). */
+size_t ssak_augment_reverb_workspace_bytes(int B, int T, int max_rir_len);
+int ssak_augment_reverb(const float* x, const int32_t* lens, const int32_t* lens_host /*host*/, int B, int T, const double* params,
+                        const double* params_host /*host*/, const ssak_audio_bank* rirs /*host struct; may be NULL without REVERB rows*/,
+                        float* y, void* workspace, size_t workspace_bytes, void* stream);
+/* Time stretch of every row: librosa.effects.time_stretch(x[:L], rate) (n_fft 2048, hop 512, periodic Hann, centred with
+ * zero padding; phase vocoder with its accumulator in fp64; iSTFT of length round(L / rate)).  y [B, T_out] with zeros
+ * past out_lens[b] = round(L / rate) (device, may be NULL); y must not alias x.
+ * workspace >= ssak_augment_time_stretch_workspace_bytes(B, T, T_out). */
+size_t ssak_augment_time_stretch_workspace_bytes(int B, int T, int T_out);
+int ssak_augment_time_stretch(const float* x, const int32_t* lens, const int32_t* lens_host /*host*/, int B, int T, const double* params,
+                              const double* params_host /*host*/, float* y, int32_t* out_lens, int T_out, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* ---- TEST-ONLY entries (not part of the product path; kept in the release library so that the parity tests run against the
  * library that ships): dropout bits of one site ------------------------------------------------------------------------
  * The engine stores no dropout mask: each site recomputes keep(seed, site, element) in its forward and backward kernels

@@ -9,11 +9,12 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 520  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 530  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -55,6 +56,17 @@ class LMBeamParams(C.Structure):  # ssak_lm_beam_params
                 ("unk_score_offset", C.c_float)]
 
 
+class AudioBank(C.Structure):  # ssak_audio_bank
+    _fields_ = [("n", C.c_int), ("data", C.c_void_p), ("offset", C.c_void_p), ("length", C.c_void_p), ("offset_host", C.c_void_p),
+                ("length_host", C.c_void_p)]
+
+
+# columns of the augmentation table (ssak_hip.h SSAK_AUG_*)
+AUG_NONE, AUG_GAIN, AUG_NOISE_MIX, AUG_REVERB = -1, 0, 1, 2
+(AUG_KIND, AUG_GAIN_DB, AUG_GAIN_LIN, AUG_SNR_DB, AUG_SNR_AMP, AUG_NOISE, AUG_NOISE_START, AUG_RIR, AUG_RIR_PEAK, AUG_RATE,
+ AUG_OUT_LEN) = range(11)
+AUG_NCOL = 11
+
 GRAD_READY_FN = C.CFUNCTYPE(None, C.c_long, C.c_long, C.c_void_p)
 
 
@@ -76,6 +88,12 @@ def _load():
         "ssak_ctc_workspace_bytes": (sz, [i32, i32, i32, i32]),
         "ssak_ctc_loss_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, sz, vp]),
         "ssak_ctc_greedy_decode": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "ssak_augment_gain_noise_workspace_bytes": (sz, [i32, i32]),
+        "ssak_augment_gain_noise": (i32, [vp, vp, vp, i32, i32, vp, vp, C.POINTER(AudioBank), vp, vp, sz, vp]),
+        "ssak_augment_reverb_workspace_bytes": (sz, [i32, i32, i32]),
+        "ssak_augment_reverb": (i32, [vp, vp, vp, i32, i32, vp, vp, C.POINTER(AudioBank), vp, vp, sz, vp]),
+        "ssak_augment_time_stretch_workspace_bytes": (sz, [i32, i32, i32]),
+        "ssak_augment_time_stretch": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, sz, vp]),
         "ssak_ctc_lm_beam_workspace_bytes": (sz, [i32, i32, i32, i32]),
         "ssak_ctc_lm_beam_decode": (i32, [vp, vp, i32, i32, i32, C.POINTER(NgramLMDesc), C.POINTER(LMBeamParams), vp, vp, vp,
                                           vp, sz, vp]),
@@ -286,6 +304,54 @@ def ctc_lm_beam_decode(logits: torch.Tensor, in_lens: torch.Tensor | None, lm: N
     check(lib.ssak_ctc_lm_beam_decode(ptr(logits), ptr(in_lens), B, F, V, C.byref(lm), C.byref(p), ptr(ids), ptr(n), ptr(score),
                                       ptr(ws), ws.numel(), stream()))
     return ids, n, score
+
+
+def _aug_args(x, lens, lens_host, params, params_host):
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()
+    lens_host = np.ascontiguousarray(lens_host, dtype=np.int32)
+    params_host = np.ascontiguousarray(params_host, dtype=np.float64)
+    assert lens_host.shape == (x.shape[0],) and params_host.shape == (x.shape[0], AUG_NCOL)
+    lens = lens.to(device=x.device, dtype=torch.int32).contiguous()
+    params = params.to(device=x.device, dtype=torch.float64).contiguous()
+    return lens, lens_host, params, params_host
+
+
+def _hp(a):
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def augment_gain_noise(x, lens, lens_host, params, params_host, noise: AudioBank | None, out=None, workspace=None):
+    """Gain / background-noise rows of the table applied to x [B,T] (``ssak_augment_gain_noise``; other rows copied) -> y [B,T]."""
+    lens, lens_host, params, params_host = _aug_args(x, lens, lens_host, params, params_host)
+    B, T = x.shape
+    y = torch.empty_like(x) if out is None else out
+    ws = workspace if workspace is not None else _ws(lib.ssak_augment_gain_noise_workspace_bytes(B, T), x.device)
+    check(lib.ssak_augment_gain_noise(ptr(x), ptr(lens), _hp(lens_host), B, T, ptr(params), _hp(params_host),
+                                      None if noise is None else C.byref(noise), ptr(y), ptr(ws), ws.numel(), stream()))
+    return y
+
+
+def augment_reverb(x, lens, lens_host, params, params_host, rirs: AudioBank | None, max_rir_len: int, out=None, workspace=None):
+    """Reverberation rows of the table applied to x [B,T] (``ssak_augment_reverb``; other rows copied) -> y [B,T]."""
+    lens, lens_host, params, params_host = _aug_args(x, lens, lens_host, params, params_host)
+    B, T = x.shape
+    y = torch.empty_like(x) if out is None else out
+    ws = workspace if workspace is not None else _ws(lib.ssak_augment_reverb_workspace_bytes(B, T, max(1, int(max_rir_len))), x.device)
+    check(lib.ssak_augment_reverb(ptr(x), ptr(lens), _hp(lens_host), B, T, ptr(params), _hp(params_host),
+                                  None if rirs is None else C.byref(rirs), ptr(y), ptr(ws), ws.numel(), stream()))
+    return y
+
+
+def augment_time_stretch(x, lens, lens_host, params, params_host, T_out: int, workspace=None):
+    """Time stretch of every row (``ssak_augment_time_stretch``) -> (y [B, T_out], out_lens [B] int32)."""
+    lens, lens_host, params, params_host = _aug_args(x, lens, lens_host, params, params_host)
+    B, T = x.shape
+    y = torch.empty((B, int(T_out)), dtype=torch.float32, device=x.device)
+    out_lens = torch.empty(B, dtype=torch.int32, device=x.device)
+    ws = workspace if workspace is not None else _ws(lib.ssak_augment_time_stretch_workspace_bytes(B, T, int(T_out)), x.device)
+    check(lib.ssak_augment_time_stretch(ptr(x), ptr(lens), _hp(lens_host), B, T, ptr(params), _hp(params_host), ptr(y), ptr(out_lens),
+                                        int(T_out), ptr(ws), ws.numel(), stream()))
+    return y, out_lens
 
 
 def lm_query(lm: NgramLMDesc, ctx_ids: torch.Tensor, words: torch.Tensor):

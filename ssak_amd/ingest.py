@@ -138,10 +138,12 @@ def read_pcm_segment(path: str, start: Optional[float] = None, end: Optional[flo
 class DeviceIngest:
     """Turns lists of (path, start, end) into normalised fp32 batches on the device."""
 
-    def __init__(self, sample_rate: int = 16000, device="cuda:0", normalize: bool = True, readers: Optional[int] = None):
+    def __init__(self, sample_rate: int = 16000, device="cuda:0", normalize: bool = True, readers: Optional[int] = None, augment=None):
         """``readers``: file-reader threads (default: the CPUs this process may use, at most 8; the reference runs 6 dataloader
-        worker processes, wav2vec_train.py:360)."""
+        worker processes, wav2vec_train.py:360).  ``augment``: a ``ssak_amd.augment.SpeechAugmentDevice``; batches staged with a
+        key (``stage(..., key=(step, positions))``) are augmented after the resample and before the normalisation."""
         self.sample_rate, self.device, self.normalize = sample_rate, torch.device(device), normalize
+        self.augment = augment
         n_cpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
         self.readers = max(1, min(8, n_cpu) if readers is None else int(readers))
         self._tables = {}
@@ -169,11 +171,20 @@ class DeviceIngest:
             self._tables[sr] = (host.to(self.device), o.value, n.value)
         return self._tables[sr]
 
-    def stage(self, items: Sequence[Tuple[str, Optional[float], Optional[float]]], labels: Optional[np.ndarray] = None):
+    def _out_len(self, sr: int, n: int) -> int:
+        """Samples after the resample (ssak_resample_sinc: ceil(new * n / orig)); host arithmetic only."""
+        if sr == self.sample_rate:
+            return n
+        o, nn, w, taps = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        hip.check(hip.lib.ssak_resample_plan(sr, self.sample_rate, C.byref(o), C.byref(nn), C.byref(w), C.byref(taps)))
+        return -(-(nn.value * n) // o.value)
+
+    def stage(self, items: Sequence[Tuple[str, Optional[float], Optional[float]]], labels: Optional[np.ndarray] = None, key=None):
         """Host part (no GPU work): the byte ranges of the segments (headers parsed once per file, in parallel) into ONE pinned
         buffer, read by the reader threads straight into their slices of it.  ``labels`` (int64 [B, L], -100 padding): appended
         to the same buffer, so that the batch's ONE H2D copy carries them too (a ``labels.to(device)`` from pageable memory on
-        the compute stream blocks the host until the previous step has drained)."""
+        the compute stream blocks the host until the previous step has drained).  ``key`` = (global step, positions in the global
+        batch): with an augmenter, the batch's augmentation table is drawn here and rides in the same buffer."""
         paths = [p for p, _, _ in items]
         infos = [wav_info(p) for p in paths]  # (first visit: ~10 us per header, later ones one stat: cheaper here than a hand-off)
         ranges = [segment_range(i, s, e) for i, (_, s, e) in zip(infos, items)]
@@ -182,10 +193,19 @@ class DeviceIngest:
         lab_off = (audio + 7) // 8 * 8
         lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int64)
         total = audio if lab is None else lab_off + lab.nbytes
+        table = aug_info = None
+        if self.augment is not None and key is not None:
+            step, positions = key
+            table = self.augment.draw(step, positions, [self._out_len(i.sample_rate, cnt) for i, (_, cnt) in zip(infos, ranges)])
+            aug_off = (total + 7) // 8 * 8
+            total = aug_off + table.params.nbytes
+            aug_info = (aug_off, table)
         slot = self._staging(total)
         pinned = slot[0]
         if lab is not None:
             pinned.numpy()[lab_off:lab_off + lab.nbytes] = lab.reshape(-1).view(np.uint8)
+        if table is not None:
+            pinned.numpy()[aug_off:total] = np.ascontiguousarray(table.params, dtype=np.float64).reshape(-1).view(np.uint8)
         offs, pos = [], 0
         for nbytes in sizes:
             offs.append(pos)
@@ -202,7 +222,7 @@ class DeviceIngest:
         except ValueError as err:  # an unreadable or truncated file: what the reference's loader raises (audio.py:49-55)
             raise RuntimeError(str(err)) from None
         meta = [(i.sample_rate, i.channels, i.sample_width, cnt) for i, (_, cnt) in zip(infos, ranges)]
-        return (pinned[:max(total, 1)], slot), offs, meta, (None if lab is None else (lab_off, lab.shape))
+        return (pinned[:max(total, 1)], slot), offs, meta, (None if lab is None else (lab_off, lab.shape)), aug_info
 
     def to_device_async(self, staged):
         """``to_device`` on the ingest's OWN stream: the H2D copy runs on a copy engine and the small decode / normalise kernels beside
@@ -218,9 +238,9 @@ class DeviceIngest:
         return out, ev
 
     def to_device(self, staged):
-        """Device part: H2D copy, PCM -> mono fp32 -> target rate -> zero-mean / unit-variance.  Returns (waves [B, T] fp32,
-        lens [B] int32), both on the device; no host synchronisation."""
-        (pinned, slot), offs, meta, lab_info = staged
+        """Device part: H2D copy, PCM -> mono fp32 -> target rate [-> augmentation] -> zero-mean / unit-variance.  Returns
+        (waves [B, T] fp32, lens [B] int32), both on the device; no host synchronisation."""
+        (pinned, slot), offs, meta, lab_info, aug_info = staged
         B = len(meta)
         dev = self.device
         with torch.cuda.device(dev):
@@ -253,6 +273,10 @@ class DeviceIngest:
                     mono = res
                 if mono is not waves:
                     waves[torch.tensor(idx, device=dev), :mono.shape[1]] = mono
+            if aug_info is not None:  # (training batches only: the table came with the batch's one H2D copy)
+                ao, table = aug_info
+                params_d = raw[ao:ao + table.params.nbytes].view(torch.float64).view(*table.params.shape)
+                waves, lens = self.augment.apply(waves, lens, table, params_d)
             if self.normalize:
                 waves = hip.wave_normalize(waves, lens)
             if lab_info is not None:
@@ -268,11 +292,13 @@ class BatchPrefetcher:
     """Iterates over batches of items; file reads + pinned staging of the next ``depth`` batches run on a background thread."""
 
     def __init__(self, ingest: DeviceIngest, batches: Sequence[Sequence[Tuple[str, Optional[float], Optional[float]]]], depth: int = 2,
-                 labels: Optional[Sequence[np.ndarray]] = None):
+                 labels: Optional[Sequence[np.ndarray]] = None, keys: Optional[Sequence[Tuple[int, Sequence[int]]]] = None):
         """``labels``: one int64 [B, L] array per batch (-100 padding); the iterator then yields (waves, lens, labels) with the labels
-        on the device too, carried by the batch's one H2D copy."""
+        on the device too, carried by the batch's one H2D copy.  ``keys``: one (global step, positions in the global batch) per
+        batch, the key of the ingest's augmentation draws."""
         self.ingest, self.batches = ingest, list(batches)
         self.labels = None if labels is None else list(labels)
+        self.keys = None if keys is None else list(keys)
         self.q: "queue.Queue" = queue.Queue(maxsize=max(1, depth))
         self.thread = threading.Thread(target=self._work, daemon=True)
         self.thread.start()
@@ -280,7 +306,7 @@ class BatchPrefetcher:
     def _work(self):
         try:
             for k, b in enumerate(self.batches):
-                self.q.put(self.ingest.stage(b, None if self.labels is None else self.labels[k]))
+                self.q.put(self.ingest.stage(b, None if self.labels is None else self.labels[k], None if self.keys is None else self.keys[k]))
         except BaseException as err:  # surfaced on the consumer side
             self.q.put(err)
         self.q.put(None)

@@ -99,7 +99,10 @@ def build_parser():
     p.add_argument("--min_duration", default=1, type=int)
     p.add_argument("--base_model", required=True, type=str, help="Model folder to adapt (HF layout)")
     p.add_argument("--no_freeze", default=False, action="store_true")
-    p.add_argument("--data_augment", default=False, action="store_true")
+    p.add_argument("--data_augment", default=False, action="store_true",
+                   help="augment every training utterance on the device (ssak_amd.augment): gain, or background noise, or reverberation, "
+                        "then a time stretch; implies --online.  Deviations from the reference: noise and RIR files must be PCM WAV; "
+                        "--batch_audio budgets count the lengths before augmentation (a batch can grow by up to 1/0.95)")
     p.add_argument("--learning_rate", type=float, default=1e-4)
     p.add_argument("--batch_size", type=int, default=8)
     p.add_argument("--num_epochs", type=int, default=20)
@@ -112,8 +115,10 @@ def build_parser():
     p.add_argument("--disable_first_eval", default=False, action="store_true")
     p.add_argument("--seed", default=69, type=int)
     p.add_argument("--eval_steps", default=400, type=int)
-    p.add_argument("--data_augment_noise", default="", type=str, help="(used only with --data_augment)")
-    p.add_argument("--data_augment_rir", default="", type=str, help="(used only with --data_augment)")
+    p.add_argument("--data_augment_noise", default="", type=str, help="(used only with --data_augment) folder of noise files, scanned "
+                   "recursively")
+    p.add_argument("--data_augment_rir", default="", type=str, help="(used only with --data_augment) ROOT/[a/rir_list,b/rir_list]; empty "
+                   "(the default here, the reference's points at its own storage) means no reverberation")
     p.add_argument("--output_dir", default=".", type=str)
     # extensions (not flags of the reference; declared last and left out of the output-folder name unless used)
     p.add_argument("--batch_audio", type=float, default=None,
@@ -183,7 +188,8 @@ def evaluate(model, tok, waves, labels, batch_size, rank: int = 0, world: int = 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.data_augment:
-        raise NotImplementedError("--data_augment (CPU DSP: audiomentations / RIR) is outside the HIP path")
+        from .augment import parse_rir_arg
+        parse_rir_arg(args.data_augment_rir)  # (the reference's RuntimeErrors before anything else happens, wav2vec_train.py:259-266)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -226,7 +232,11 @@ def main(argv=None):
     # decode / mono mix / resampling / normalisation on the device (ssak_amd.ingest)
     if args.online:
         from .ingest import BatchPrefetcher, DeviceIngest
-        ingest = DeviceIngest(16000, dev)
+        augmenter = None
+        if args.data_augment:  # (every rank: the draws are keyed on the global step and batch position, not on the rank)
+            from .augment import SpeechAugmentDevice
+            augmenter = SpeechAugmentDevice(args.data_augment_noise or None, args.data_augment_rir, 16000, args.seed, dev)
+        ingest = DeviceIngest(16000, dev, augment=augmenter)
         tw = None
         tl = [tok.encode(remove_special_words(u.text)) for u in train_u]
         train_len = [int(u.duration * 16000) for u in train_u]
@@ -331,7 +341,8 @@ def main(argv=None):
                 continue
         if args.online:
             feed = BatchPrefetcher(ingest, [[(train_u[i].path, train_u[i].start or None, train_u[i].end or None) for i in m] for _, m in plan if m],
-                                   labels=[pad_labels([tl[i] for i in m]) for _, m in plan if m])  # (the labels ride with the audio's H2D copy)
+                                   labels=[pad_labels([tl[i] for i in m]) for _, m in plan if m],  # (the labels ride with the audio's H2D copy)
+                                   keys=[(step + k, [w.index(i) for i in m]) for k, (w, m) in enumerate(plan) if m])
             feed = iter(feed)
         else:
             feed = (pad_waves([tw[i] for i in m]) for _, m in plan if m)
