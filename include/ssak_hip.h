@@ -619,6 +619,37 @@ int ssak_debug_dropout_mask(uint64_t seed, uint32_t site, float p, long rows, in
                             void* stream);
 int ssak_debug_attention_dropout_mask(uint64_t seed, uint32_t site, float p, int B, int nh, int F, uint8_t* keep, void* stream);
 
+/* ---- TEST-ONLY entries (ABI 540): the row kernels of norm_act.hip, one launch each -------------------------------------
+ * Each calls the template the engine calls, instantiated for dtype 0 = bf16 (the engine) or 1 = fp32 (the fp32-exact mode);
+ * activations are void* of that type, [M, C] row-major.  A dropout site is (site id, p), all sites under the launch's one
+ * seed (keep bits: ssak_debug_dropout_mask on the site's [M, C] / [rows, ld] tensor); p = 0 turns a site off.
+ * LayerNorm forward: r = mid(res + pre(y)) (rounded to the storage type, and stored, when r_out is given; r_out may alias y),
+ * out = post(gelu?(LN(r) * gamma + beta)) with the biased variance, mean / rstd [M] fp32 (both or neither).  out = NULL is
+ * the dropout-only pass (no LN: gamma, beta, mean and post must be off).  y or res may be NULL.
+ * LayerNorm backward (workspace >= ssak_debug_layernorm_bwd_workspace_bytes(C)): a = post(g1 + g2) [* gelu'(xhat gamma +
+ * post_gelu_beta)], dr = mid(LN_bwd(a) + g_res), dy = pre(dr) (NULL: not written); dgamma, dbeta [C] += the column sums,
+ * dy_colsum [C] += those of dy (needs dy).  queued != 0 sends the second stage of the column sums through the engine's
+ * deferred-reduction queue (one flush at the end of the call) instead of its own finalize launch; both sum in the same order.
+ * Softmax forward: P [rows, ld] over the first min(klens[row / rows_per_batch], cols) keys (klens NULL: all cols), other
+ * columns 0, a row with no valid key all 0; Pd = drop(P) (may be NULL when p = 0).  Backward: dS = P * (dP - sum(P * dP)),
+ * dP = drop(dPd), columns [cols, ld) 0.  cols <= ld <= 1536, ld a multiple of 8.
+ * GELU: y = gelu(x), dydx = gelu'(x) [n] fp32 as the kernels of that dtype compute them (bf16: the logistic fit of common.h;
+ * fp32: erff).  Bad arguments (C not a multiple of 8 or > 1536, ld > 1536, M <= 0, p outside [0, 1), ...) are SSAK_ERR_INVALID. */
+int ssak_debug_layernorm_fwd(const void* y, const void* res, const float* gamma, const float* beta, void* r_out, void* out, float* mean,
+                             float* rstd, int M, int C, float eps, uint64_t seed, uint32_t pre_site, float pre_p, uint32_t mid_site,
+                             float mid_p, uint32_t post_site, float post_p, int post_gelu, int dtype, void* stream);
+size_t ssak_debug_layernorm_bwd_workspace_bytes(int C);
+int ssak_debug_layernorm_bwd(const void* g1, const void* g2, const void* r, const float* mean, const float* rstd, const float* gamma,
+                             const void* g_res, void* dr, void* dy, float* dgamma, float* dbeta, float* dy_colsum,
+                             const float* post_gelu_beta, int M, int C, uint64_t seed, uint32_t pre_site, float pre_p, uint32_t mid_site,
+                             float mid_p, uint32_t post_site, float post_p, int queued, int dtype, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int ssak_debug_softmax_fwd(const void* S, void* P, void* Pd, const int32_t* klens, int rows, int cols, int ld, int rows_per_batch,
+                           uint64_t seed, uint32_t site, float p, int dtype, void* stream);
+int ssak_debug_softmax_bwd(const void* dPd, const void* P, void* dS, int rows, int cols, int ld, uint64_t seed, uint32_t site, float p,
+                           int dtype, void* stream);
+int ssak_debug_gelu(const float* x, long n, float* y, float* dydx, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

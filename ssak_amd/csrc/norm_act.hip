@@ -560,7 +560,10 @@ __global__ __launch_bounds__(ROW_THREADS) void softmax_fwd_kernel(const SoftmaxP
       v[i][k] = (v[i][k] == -INFINITY) ? 0.f : __expf(v[i][k] - mx);
       sum += v[i][k];
     }
-  const float inv = 1.f / wave_sum(sum);
+  // a row with no valid key (klens[b] = 0: an utterance shorter than the feature encoder's receptive field) comes out as zeros,
+  // as in the fused attention kernels, instead of 0 * (1 / 0) = NaN
+  const float tot = wave_sum(sum);
+  const float inv = tot > 0.f ? 1.f / tot : 0.f;
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
     const int ch = lane + 64 * i;
@@ -1080,4 +1083,117 @@ extern "C" int ssak_debug_attention_dropout_mask(uint64_t seed, uint32_t site, f
                                                  void* stream) {
   SSAK_REQUIRE(keep && B > 0 && nh > 0 && F > 0, "debug_attention_dropout_mask: bad arguments");
   return ssak_debug_dropout_mask(seed, site, p, (long)B * nh * F, F, keep, nullptr, stream);
+}
+
+// ---- debug: the row kernels of this file, one launch each (tests/test_gpu_rowwise.py holds them to the float64 restatement
+// tests/rowwise_ref.py).  They call the same templates the engine calls, with dtype 0 = bf16 (the engine) or 1 = float (the
+// fp32-exact mode); activations are passed as void* of that type.  A dropout site is (site id, p) under the launch's one seed,
+// as the engine passes them (every site of a step shares its seed).  Nothing on the hot path calls these.
+namespace {
+DropSpec debug_site(uint64_t seed, uint32_t site, float p) {
+  DropSpec d;
+  d.seed = seed;
+  d.stream = site;
+  d.p = p;
+  return d;
+}
+bool debug_p_ok(float p) { return p >= 0.f && p < 1.f; }
+
+template <typename T>
+__global__ void debug_gelu_kernel(const float* __restrict__ x, long n, float* __restrict__ y, float* __restrict__ dydx) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (y) y[i] = gelu_s<T>(x[i]);
+  if (dydx) dydx[i] = gelu_grad_s<T>(x[i]);
+}
+}  // namespace
+
+extern "C" int ssak_debug_layernorm_fwd(const void* y, const void* res, const float* gamma, const float* beta, void* r_out, void* out,
+                                        float* mean, float* rstd, int M, int C, float eps, uint64_t seed, uint32_t pre_site, float pre_p,
+                                        uint32_t mid_site, float mid_p, uint32_t post_site, float post_p, int post_gelu, int dtype,
+                                        void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_layernorm_fwd: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(M > 0 && C > 0 && (C & 7) == 0 && C <= 1536, "debug_layernorm_fwd: M=%d C=%d (C a multiple of 8, <= 1536)", M, C);
+  SSAK_REQUIRE(y || res, "debug_layernorm_fwd: neither y nor res");
+  SSAK_REQUIRE(out || r_out, "debug_layernorm_fwd: neither out nor r_out");
+  SSAK_REQUIRE(!out || (gamma && beta), "debug_layernorm_fwd: out needs gamma and beta");
+  SSAK_REQUIRE(!mean == !rstd, "debug_layernorm_fwd: mean and rstd go together");
+  SSAK_REQUIRE(out || (!mean && !post_gelu && post_p == 0.f), "debug_layernorm_fwd: statistics, GELU and post-dropout need out");
+  SSAK_REQUIRE(debug_p_ok(pre_p) && debug_p_ok(mid_p) && debug_p_ok(post_p), "debug_layernorm_fwd: p outside [0, 1)");
+  SSAK_REQUIRE(y || pre_p == 0.f, "debug_layernorm_fwd: pre-dropout without y");
+  const DropSpec pre = debug_site(seed, pre_site, pre_p), mid = debug_site(seed, mid_site, mid_p), post = debug_site(seed, post_site, post_p);
+  const hipStream_t st = (hipStream_t)stream;
+  if (dtype == 0)
+    return k_layernorm_fwd_t<bf16>((const bf16*)y, (const bf16*)res, gamma, beta, (bf16*)r_out, (bf16*)out, mean, rstd, M, C, eps, pre,
+                                   post, st, mid, post_gelu != 0);
+  return k_layernorm_fwd_t<float>((const float*)y, (const float*)res, gamma, beta, (float*)r_out, (float*)out, mean, rstd, M, C, eps,
+                                  pre, post, st, mid, post_gelu != 0);
+}
+
+extern "C" size_t ssak_debug_layernorm_bwd_workspace_bytes(int C) { return C > 0 ? (size_t)LN_BWD_BLOCKS * 3 * C * sizeof(float) : 0; }
+
+extern "C" int ssak_debug_layernorm_bwd(const void* g1, const void* g2, const void* r, const float* mean, const float* rstd,
+                                        const float* gamma, const void* g_res, void* dr, void* dy, float* dgamma, float* dbeta,
+                                        float* dy_colsum, const float* post_gelu_beta, int M, int C, uint64_t seed, uint32_t pre_site,
+                                        float pre_p, uint32_t mid_site, float mid_p, uint32_t post_site, float post_p, int queued,
+                                        int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_layernorm_bwd: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(M > 0 && C > 0 && (C & 7) == 0 && C <= 1536, "debug_layernorm_bwd: M=%d C=%d (C a multiple of 8, <= 1536)", M, C);
+  SSAK_REQUIRE(g1 && r && mean && rstd && gamma && dr && dgamma && dbeta, "debug_layernorm_bwd: null operand");
+  SSAK_REQUIRE(!dy_colsum || dy, "debug_layernorm_bwd: dy_colsum needs dy");
+  SSAK_REQUIRE(debug_p_ok(pre_p) && debug_p_ok(mid_p) && debug_p_ok(post_p), "debug_layernorm_bwd: p outside [0, 1)");
+  SSAK_REQUIRE(workspace && workspace_bytes >= ssak_debug_layernorm_bwd_workspace_bytes(C), "debug_layernorm_bwd: workspace too small");
+  const DropSpec pre = debug_site(seed, pre_site, pre_p), mid = debug_site(seed, mid_site, mid_p), post = debug_site(seed, post_site, post_p);
+  const hipStream_t st = (hipStream_t)stream;
+  ReduceSink sink;
+  ReduceSink* const saved = g_reduce_sink;
+  if (queued) g_reduce_sink = &sink;  // the engine's path: the column sums' second stage waits in the sink for one flush
+  int rc;
+  if (dtype == 0)
+    rc = k_layernorm_bwd_t<bf16>((const bf16*)g1, (const bf16*)g2, (const bf16*)r, mean, rstd, gamma, (const bf16*)g_res, (bf16*)dr,
+                                 (bf16*)dy, dgamma, dbeta, (float*)workspace, M, C, pre, post, st, mid, dy_colsum, post_gelu_beta);
+  else
+    rc = k_layernorm_bwd_t<float>((const float*)g1, (const float*)g2, (const float*)r, mean, rstd, gamma, (const float*)g_res,
+                                  (float*)dr, (float*)dy, dgamma, dbeta, (float*)workspace, M, C, pre, post, st, mid, dy_colsum,
+                                  post_gelu_beta);
+  g_reduce_sink = saved;
+  if (rc != SSAK_OK || !queued) return rc;
+  SSAK_REQUIRE(sink.n == (dy_colsum ? 3 : 2), "debug_layernorm_bwd: %d column sums queued", sink.n);
+  return k_reduce_flush(sink, st);
+}
+
+extern "C" int ssak_debug_softmax_fwd(const void* S, void* P, void* Pd, const int32_t* klens, int rows, int cols, int ld,
+                                      int rows_per_batch, uint64_t seed, uint32_t site, float p, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_softmax_fwd: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(rows > 0 && cols > 0 && ld >= cols && (ld & 7) == 0 && ld <= 1536, "debug_softmax_fwd: rows=%d cols=%d ld=%d (ld >= cols, "
+               "a multiple of 8, <= 1536)", rows, cols, ld);
+  SSAK_REQUIRE(S && P, "debug_softmax_fwd: null operand");
+  SSAK_REQUIRE(!klens || rows_per_batch > 0, "debug_softmax_fwd: klens needs rows_per_batch > 0");
+  SSAK_REQUIRE(debug_p_ok(p) && (Pd || p == 0.f), "debug_softmax_fwd: p outside [0, 1) or dropout without Pd");
+  const DropSpec d = debug_site(seed, site, p);
+  if (dtype == 0)
+    return k_softmax_fwd_t<bf16>((const bf16*)S, (bf16*)P, (bf16*)Pd, klens, rows, cols, ld, rows_per_batch, d, (hipStream_t)stream);
+  return k_softmax_fwd_t<float>((const float*)S, (float*)P, (float*)Pd, klens, rows, cols, ld, rows_per_batch, d, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_softmax_bwd(const void* dPd, const void* P, void* dS, int rows, int cols, int ld, uint64_t seed, uint32_t site,
+                                      float p, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_softmax_bwd: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(rows > 0 && cols > 0 && ld >= cols && (ld & 7) == 0 && ld <= 1536, "debug_softmax_bwd: rows=%d cols=%d ld=%d (ld >= cols, "
+               "a multiple of 8, <= 1536)", rows, cols, ld);
+  SSAK_REQUIRE(dPd && P && dS, "debug_softmax_bwd: null operand");
+  SSAK_REQUIRE(debug_p_ok(p), "debug_softmax_bwd: p outside [0, 1)");
+  const DropSpec d = debug_site(seed, site, p);
+  if (dtype == 0) return k_softmax_bwd_t<bf16>((const bf16*)dPd, (const bf16*)P, (bf16*)dS, rows, cols, ld, d, (hipStream_t)stream);
+  return k_softmax_bwd_t<float>((const float*)dPd, (const float*)P, (float*)dS, rows, cols, ld, d, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_gelu(const float* x, long n, float* y, float* dydx, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_gelu: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(x && n > 0 && (y || dydx), "debug_gelu: bad arguments");
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  if (dtype == 0) debug_gelu_kernel<bf16><<<grid, 256, 0, (hipStream_t)stream>>>(x, n, y, dydx);
+  else debug_gelu_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(x, n, y, dydx);
+  SSAK_LAUNCH_CHECK();
+  return SSAK_OK;
 }

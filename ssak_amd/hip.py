@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 530  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 540  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -170,6 +170,14 @@ def _load():
         "ssak_comm_destroy": (i32, [vp]),
         "ssak_debug_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, C.c_long, i32, vp, C.POINTER(f32), vp]),
         "ssak_debug_attention_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, i32, i32, i32, vp, vp]),
+        "ssak_debug_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, C.c_uint64, C.c_uint32, f32, C.c_uint32,
+                                            f32, C.c_uint32, f32, i32, i32, vp]),
+        "ssak_debug_layernorm_bwd_workspace_bytes": (sz, [i32]),
+        "ssak_debug_layernorm_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_uint64, C.c_uint32, f32,
+                                            C.c_uint32, f32, C.c_uint32, f32, i32, i32, vp, sz, vp]),
+        "ssak_debug_softmax_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, C.c_uint64, C.c_uint32, f32, i32, vp]),
+        "ssak_debug_softmax_bwd": (i32, [vp, vp, vp, i32, i32, i32, C.c_uint64, C.c_uint32, f32, i32, vp]),
+        "ssak_debug_gelu": (i32, [vp, C.c_long, vp, vp, i32, vp]),
     }
     lib.ssak_version.restype = i32
     got = lib.ssak_version()
@@ -553,3 +561,54 @@ def attention_bwd_bias(qkv, ctx, lse, dctx, B: int, F: int, nh: int, klens=None,
     check(lib.ssak_attention_bwd_bias(ptr(qkv), ptr(ctx), ptr(lse), ptr(klens), ptr(dctx), ptr(delta), ptr(dqkv), ptr(bias_grad), B, F,
                                       nh, H, float(drop_p), seed, stream_id, ptr(ws), nbytes, stream()))
     return dqkv, bias_grad
+
+
+# ------------------------------------------------------------------ test-only: the row kernels of norm_act.hip (ABI 540)
+def _row_dtype(t: torch.Tensor) -> int:
+    if t.dtype == torch.bfloat16:
+        return 0
+    if t.dtype == torch.float32:
+        return 1
+    raise TypeError(f"row kernels take bf16 or fp32 activations, not {t.dtype}")
+
+
+def debug_layernorm_fwd(y, res, gamma, beta, r_out=None, out=None, mean=None, rstd=None, *, eps=1e-5, seed=0, pre=(0, 0.0),
+                        mid=(0, 0.0), post=(0, 0.0), post_gelu=False):
+    """One ``k_layernorm_fwd_t`` launch into the caller's buffers (``ssak_debug_layernorm_fwd``).  Sites are (site id, p)."""
+    x = y if y is not None else res
+    M, C = x.shape
+    check(lib.ssak_debug_layernorm_fwd(ptr(y), ptr(res), ptr(gamma), ptr(beta), ptr(r_out), ptr(out), ptr(mean), ptr(rstd), M, C,
+                                       float(eps), seed, pre[0], float(pre[1]), mid[0], float(mid[1]),
+                                       post[0], float(post[1]), int(bool(post_gelu)), _row_dtype(x), stream()))
+
+
+def debug_layernorm_bwd(g1, g2, r, mean, rstd, gamma, g_res, dr, dy, dgamma, dbeta, dy_colsum=None, post_gelu_beta=None, *, seed=0,
+                        pre=(0, 0.0), mid=(0, 0.0), post=(0, 0.0), queued=False, workspace=None):
+    """One ``k_layernorm_bwd_t`` launch (+ its column-sum second stage, queued or direct) into the caller's buffers."""
+    M, Cc = r.shape
+    nbytes = lib.ssak_debug_layernorm_bwd_workspace_bytes(Cc)
+    ws = workspace if workspace is not None else _ws(nbytes, r.device)
+    check(lib.ssak_debug_layernorm_bwd(ptr(g1), ptr(g2), ptr(r), ptr(mean), ptr(rstd), ptr(gamma), ptr(g_res), ptr(dr), ptr(dy),
+                                       ptr(dgamma), ptr(dbeta), ptr(dy_colsum), ptr(post_gelu_beta), M, Cc, seed, pre[0], float(pre[1]),
+                                       mid[0], float(mid[1]), post[0], float(post[1]), int(bool(queued)), _row_dtype(r), ptr(ws),
+                                       ws.numel(), stream()))
+
+
+def debug_softmax_fwd(S, P, Pd, klens, cols: int, rows_per_batch: int = 1, *, seed=0, site=0, p=0.0):
+    """``k_softmax_fwd_t`` on S [rows, ld] (ld = row stride) into P (and Pd)."""
+    rows, ld = S.shape
+    check(lib.ssak_debug_softmax_fwd(ptr(S), ptr(P), ptr(Pd), ptr(klens), rows, cols, ld, rows_per_batch, seed, site, float(p),
+                                     _row_dtype(S), stream()))
+
+
+def debug_softmax_bwd(dPd, P, dS, cols: int, *, seed=0, site=0, p=0.0):
+    rows, ld = P.shape
+    check(lib.ssak_debug_softmax_bwd(ptr(dPd), ptr(P), ptr(dS), rows, cols, ld, seed, site, float(p), _row_dtype(P), stream()))
+
+
+def debug_gelu(x: torch.Tensor, dtype: torch.dtype):
+    """gelu(x), gelu'(x) [fp32] as the kernels of storage type ``dtype`` evaluate them."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+    y, d = torch.empty_like(x), torch.empty_like(x)
+    check(lib.ssak_debug_gelu(ptr(x), x.numel(), ptr(y), ptr(d), 0 if dtype == torch.bfloat16 else 1, stream()))
+    return y, d
