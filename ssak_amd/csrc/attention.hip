@@ -53,19 +53,29 @@ struct AttnParams {
 };
 
 __device__ __forceinline__ float shfl_xor_f(float v, int m) { return __shfl_xor(v, m, 64); }
-// max over the four 16-lane groups of a wave (lanes l, l ^ 16, l ^ 32, l ^ 48), the result in all of them: two VALU swaps
-// (v_permlane16_swap / v_permlane32_swap of the value with a copy of itself leave {r0 r0 r2 r2 | r1 r1 r3 r3} and
-// {lo lo | hi hi}) instead of two ds_bpermute round trips through the LDS crossbar in the softmax's dependent chain
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-__device__ __forceinline__ float max_over_lane_groups(float v) {
-  const unsigned b = __builtin_bit_cast(unsigned, v);
-  u32x2_t t = __builtin_amdgcn_permlane16_swap(b, b, false, false);
-  float m;  // (asm: no canonicalising v_max x, x in front)
-  asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(__builtin_bit_cast(float, t[0])), "v"(__builtin_bit_cast(float, t[1])));
-  const unsigned c = __builtin_bit_cast(unsigned, m);
-  t = __builtin_amdgcn_permlane32_swap(c, c, false, false);
+// The exponent offset of the online softmax (any value works as long as no exp2 overflows: it cancels in O / l and lse).  It was
+// meant to be the tile's maximum over the four 16-lane groups of a wave (lanes l, l ^ 16, l ^ 32, l ^ 48), taken
+// with v_permlane16_swap / v_permlane32_swap of the value with a copy of itself -- but __builtin_amdgcn_permlane{16,32}_swap
+// given the same value twice has both of its results folded into the first (hipcc for gfx950 emits `v_permlane16_swap v1, v2`,
+// then reads v1 for both), so every lane got lane group 0's maximum: 16 of the tile's 64 keys.  That overflowed exp2 (ctx = NaN,
+// lse = inf) once another group's keys scored 128 / c2 above them (tests/test_gpu_attention.py, the "large" regime).  The
+// offset is now max(group 0's maximum, the true maximum - 12 / c2): exp2 arguments stay <= 12, and rows whose maxima lie within
+// 12 (log2 units) of each other -- every realistic one -- keep the offset, and so the results, they had.  The price of an offset
+// below the maximum: a rescale factor can underflow up to 2^12 sooner, so terms below 2^-114 of the row's largest probability
+// may be lost (with the true maximum: below 2^-126).  The swaps are inline asm, each result read as written.
+__device__ __forceinline__ float softmax_offset(float v, float slack) {
+  float x = v, y = v;  // (s_nop 1: the two wait states a VALU write needs before a permlane swap reads it)
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));  // x = {r0 r0 r2 r2}, y = {r1 r1 r3 r3}
+  float pm;  // (asm: no canonicalising v_max x, x in front)
+  asm("v_max_f32 %0, %1, %2" : "=v"(pm) : "v"(x), "v"(y));
+  float a = pm, b = pm;
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));  // {lo lo | hi hi}
+  float all;
+  asm("v_max_f32 %0, %1, %2" : "=v"(all) : "v"(a), "v"(b));
+  float g0 = x, g2 = x;
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(g0), "+v"(g2));  // g0 = {r0 r0 | r0 r0}
   float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(__builtin_bit_cast(float, t[0])), "v"(__builtin_bit_cast(float, t[1])));
+  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(g0), "v"(all - slack));
   return r;
 }
 // max of two without the canonicalising v_max x, x that fmaxf puts in front of values it cannot prove canonical (MFMA results,
@@ -316,6 +326,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnParams p) {
     l_run[qs] = 0.f;
   }
   const float c2 = p.scale * 1.4426950408889634f;  // softmax scale x log2(e)
+  const float slack = 12.f / c2;  // softmax_offset: exp2 arguments <= 12
   const uint32_t thi = p.thresh16 << 16;
   uint32_t rowseed[NQS];
 #pragma unroll
@@ -389,7 +400,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnParams p) {
         else
           mx = max2_nc(mx, s[qs][ks][3]);
       }
-      mx = max_over_lane_groups(mx);
+      mx = softmax_offset(mx, slack);
       // key 0 is never masked (kl >= 1 whenever a tile is processed), so the running maximum is finite from the first tile on
       const float m_new = max2_nc(m_run[qs], mx);
       const float mc = m_new * c2;
