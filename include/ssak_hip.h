@@ -650,6 +650,34 @@ int ssak_debug_softmax_bwd(const void* dPd, const void* P, void* dS, int rows, i
                            int dtype, void* stream);
 int ssak_debug_gelu(const float* x, long n, float* y, float* dydx, int dtype, void* stream);
 
+/* ---- TEST-ONLY entries (ABI 550): the grouped positional convolution (posconv.hip, conv_frontend.hip), one stage each ---
+ * Each calls the k_posconv_* launch functions the engine calls, with the engine's arguments (rows_per_group = K / 2 +
+ * B (F + K) + K, batch stride F + K, lead = K / 2).  H hidden size, G groups, cg = H / G, K taps; activations h / dpre / out /
+ * pre are [B * F, H] row-major.  dtype 0 = bf16 (the engine), 1 = fp32 (the fp32-exact mode).
+ * prepare: g [K], v [H][cg][K] fp32 -> wf[o][k][c] and wb[group][c][K - 1 - k][n] (o = group * cg + n), both = g[k] v / ||v_k||
+ *   in `dtype`; norms: (2 + H) K floats, [K] ||v_k||^2 first, the rest scratch.
+ * pack: h -> pg [G][K / 2 + B (F + K) + K][cg] of `dtype`: K / 2 zero rows, then per utterance F frames and K zero rows, then K
+ *   zero rows.
+ * direct (bf16): out = [gelu](conv(h, w) + bias) for w in the wf layout (the forward: row0 = 0, pre = the pre-activation,
+ *   may be NULL) or in the wb layout (the input gradient: row0 = 1 for even K, no bias / gelu / pre); pack + fragment order +
+ *   posconv_direct_kernel.
+ * wgrad (bf16): dwf [G][K * cg][cg] fp32 = sum over time of h[t + k - K / 2][c] dpre[t][n] (overwritten); pack of both +
+ *   posconv_wgrad_kernel + posconv_wgrad_sum_kernel.
+ * weight_bwd: dg [K] += , dv [H][cg][K] += the weight-norm backward of dwf; norms as left by prepare for the same g, v, of
+ *   prepare's (2 + H) K floats: norms[0 .. K) is read, norms[K .. (2 + H) K) is overwritten as scratch.
+ * workspace >= ssak_debug_posconv_workspace_bytes(B, F, H, G, K) (0 for a geometry the direct kernels are not built for:
+ * cg = 48 or 64; K a multiple of 16 for cg = 48, of 8 for cg = 64).  Unsupported geometries are SSAK_ERR_INVALID. */
+int ssak_debug_posconv_prepare(const float* g, const float* v, void* wf, void* wb, float* norms, int H, int G, int K, int dtype,
+                               void* stream);
+int ssak_debug_posconv_pack(const void* h, void* pg, int B, int F, int H, int G, int K, int dtype, void* stream);
+size_t ssak_debug_posconv_workspace_bytes(int B, int F, int H, int G, int K);
+int ssak_debug_posconv_direct(const void* h, const void* w, const float* bias, void* out, void* pre, int B, int F, int H, int G, int K,
+                              int row0, int gelu, void* workspace, size_t workspace_bytes, void* stream);
+int ssak_debug_posconv_wgrad(const void* h, const void* dpre, float* dwf, int B, int F, int H, int G, int K, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int ssak_debug_posconv_weight_bwd(const float* dwf, const float* g, const float* v, float* norms, float* dg, float* dv, int H, int G,
+                                  int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ void ssak_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int ssak_version(void) { return 540; }  // ssak_debug_layernorm_* / _softmax_* / _gelu (INTEGRATION.md "ABI 540")
+extern "C" int ssak_version(void) { return 550; }  // ssak_debug_posconv_* (INTEGRATION.md "ABI 550")
 extern "C" const char* ssak_last_error(void) { return g_err; }
 
 // ---- optional per-launch timing (bench.py's roofline leg): HIP events around launches, on the launch's own stream ----

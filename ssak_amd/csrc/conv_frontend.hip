@@ -1005,3 +1005,33 @@ extern "C" size_t ssak_conv0_workspace_bytes(int B, int T, int C) {
   if (T < KS0) return 0;
   return k_conv0_stats_doubles(B, (T - KS0) / ST0 + 1, C) * sizeof(double);
 }
+
+// ---- debug: the positional convolution's weight preparation, packing and weight-norm backward, one call each
+// (tests/test_gpu_posconv.py; the direct kernels' entries are in posconv.hip).  Nothing on the hot path calls these.
+namespace {
+bool pc_debug_shape(int H, int G, int K) { return H > 0 && G > 0 && K > 0 && K <= 1024 && H % G == 0 && ((H / G) & 7) == 0; }
+}  // namespace
+
+extern "C" int ssak_debug_posconv_prepare(const float* g, const float* v, void* wf, void* wb, float* norms, int H, int G, int K, int dtype,
+                                          void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_posconv_prepare: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(g && v && wf && wb && norms, "debug_posconv_prepare: null pointer");
+  SSAK_REQUIRE(pc_debug_shape(H, G, K), "debug_posconv_prepare: H=%d G=%d K=%d", H, G, K);
+  if (dtype == 0) return k_posconv_prepare_t<bf16>(g, v, (bf16*)wf, (bf16*)wb, norms, H, G, K, (hipStream_t)stream);
+  return k_posconv_prepare_t<float>(g, v, (float*)wf, (float*)wb, norms, H, G, K, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_posconv_pack(const void* h, void* pg, int B, int F, int H, int G, int K, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_posconv_pack: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(h && pg, "debug_posconv_pack: null pointer");
+  SSAK_REQUIRE(B > 0 && F > 0 && pc_debug_shape(H, G, K), "debug_posconv_pack: B=%d F=%d H=%d G=%d K=%d", B, F, H, G, K);
+  if (dtype == 0) return k_posconv_pack_t<bf16>((const bf16*)h, (bf16*)pg, B, F, H, G, K, (hipStream_t)stream);
+  return k_posconv_pack_t<float>((const float*)h, (float*)pg, B, F, H, G, K, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_posconv_weight_bwd(const float* dwf, const float* g, const float* v, float* norms, float* dg, float* dv, int H,
+                                             int G, int K, void* stream) {
+  SSAK_REQUIRE(dwf && g && v && norms && dg && dv, "debug_posconv_weight_bwd: null pointer");
+  SSAK_REQUIRE(pc_debug_shape(H, G, K), "debug_posconv_weight_bwd: H=%d G=%d K=%d", H, G, K);
+  return k_posconv_weight_bwd(dwf, g, v, norms, dg, dv, H, G, K, (hipStream_t)stream);
+}

@@ -456,3 +456,68 @@ int k_posconv_wgrad_direct(const bf16* x, const bf16* dy, long rows_per_group, l
   SSAK_LAUNCH_CHECK();
   return SSAK_OK;
 }
+
+// ---- debug: the direct kernels of this file, one stage each (tests/test_gpu_posconv.py holds them to the float64 restatement
+// tests/posconv_ref.py).  The same pack / fragment / launch functions the engine calls (w2v2_engine.hip, a6 and its backward), with
+// the engine's packed geometry; the caller's workspace takes the place of the engine's arena.  Nothing on the hot path calls these.
+namespace {
+struct PcDebugWs {
+  size_t x, dy, frag, scratch, total;  // byte offsets: packed input | packed gradient | fragment-ordered weights | wgrad partials
+  long rows_per_group;
+};
+bool pc_debug_geometry(int B, int F, int H, int G, int K) {
+  return B > 0 && F > 0 && k_posconv_direct_supported(H, G, K) && K % (H / G == 48 ? PwGeom<48>::TT : PwGeom<64>::TT) == 0 &&
+         (long)B * F < (1L << 30);
+}
+PcDebugWs pc_debug_ws(int B, int F, int H, int G, int K) {
+  auto up = [](size_t n) { return (n + 255) / 256 * 256; };
+  PcDebugWs w;
+  w.rows_per_group = K / 2 + (long)B * (F + K) + K;
+  const size_t packed = up((size_t)G * w.rows_per_group * (H / G) * sizeof(bf16));
+  w.x = 0;
+  w.dy = packed;
+  w.frag = 2 * packed;
+  w.scratch = w.frag + up((size_t)H * K * (H / G) * sizeof(bf16));
+  w.total = w.scratch + up(k_posconv_wgrad_scratch_floats(H, G, K) * sizeof(float));
+  return w;
+}
+}  // namespace
+
+extern "C" size_t ssak_debug_posconv_workspace_bytes(int B, int F, int H, int G, int K) {
+  return pc_debug_geometry(B, F, H, G, K) ? pc_debug_ws(B, F, H, G, K).total : 0;
+}
+
+extern "C" int ssak_debug_posconv_direct(const void* h, const void* w, const float* bias, void* out, void* pre, int B, int F, int H, int G,
+                                         int K, int row0, int gelu, void* workspace, size_t workspace_bytes, void* stream) {
+  SSAK_REQUIRE(h && w && out && workspace, "debug_posconv_direct: null pointer");
+  SSAK_REQUIRE(pc_debug_geometry(B, F, H, G, K), "debug_posconv_direct: B=%d F=%d H=%d G=%d K=%d not built", B, F, H, G, K);
+  SSAK_REQUIRE(row0 >= 0 && row0 <= 1, "debug_posconv_direct: row0=%d (0 forward, 1 input gradient)", row0);
+  const PcDebugWs ws = pc_debug_ws(B, F, H, G, K);
+  SSAK_REQUIRE(workspace_bytes >= ws.total, "debug_posconv_direct: workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)workspace;
+  bf16* px = (bf16*)(base + ws.x);
+  bf16* frag = (bf16*)(base + ws.frag);
+  int rc = k_posconv_pack_t<bf16>((const bf16*)h, px, B, F, H, G, K, st);
+  if (rc != SSAK_OK) return rc;
+  rc = k_posconv_frag_weights((const bf16*)w, frag, H, G, K, st);
+  if (rc != SSAK_OK) return rc;
+  return k_posconv_direct(px, ws.rows_per_group, row0, frag, bias, (bf16*)out, (bf16*)pre, B, F, H, G, K, gelu != 0, st);
+}
+
+extern "C" int ssak_debug_posconv_wgrad(const void* h, const void* dpre, float* dwf, int B, int F, int H, int G, int K, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  SSAK_REQUIRE(h && dpre && dwf && workspace, "debug_posconv_wgrad: null pointer");
+  SSAK_REQUIRE(pc_debug_geometry(B, F, H, G, K), "debug_posconv_wgrad: B=%d F=%d H=%d G=%d K=%d not built", B, F, H, G, K);
+  const PcDebugWs ws = pc_debug_ws(B, F, H, G, K);
+  SSAK_REQUIRE(workspace_bytes >= ws.total, "debug_posconv_wgrad: workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)workspace;
+  bf16* px = (bf16*)(base + ws.x);
+  bf16* pdy = (bf16*)(base + ws.dy);
+  int rc = k_posconv_pack_t<bf16>((const bf16*)h, px, B, F, H, G, K, st);
+  if (rc != SSAK_OK) return rc;
+  rc = k_posconv_pack_t<bf16>((const bf16*)dpre, pdy, B, F, H, G, K, st);
+  if (rc != SSAK_OK) return rc;
+  return k_posconv_wgrad_direct(px, pdy, ws.rows_per_group, (long)B * (F + K), K / 2, dwf, (float*)(base + ws.scratch), H, G, K, st);
+}

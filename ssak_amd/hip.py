@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 540  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 550  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -178,6 +178,12 @@ def _load():
         "ssak_debug_softmax_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, C.c_uint64, C.c_uint32, f32, i32, vp]),
         "ssak_debug_softmax_bwd": (i32, [vp, vp, vp, i32, i32, i32, C.c_uint64, C.c_uint32, f32, i32, vp]),
         "ssak_debug_gelu": (i32, [vp, C.c_long, vp, vp, i32, vp]),
+        "ssak_debug_posconv_prepare": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        "ssak_debug_posconv_pack": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+        "ssak_debug_posconv_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+        "ssak_debug_posconv_direct": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+        "ssak_debug_posconv_wgrad": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
+        "ssak_debug_posconv_weight_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     }
     lib.ssak_version.restype = i32
     got = lib.ssak_version()
@@ -612,3 +618,52 @@ def debug_gelu(x: torch.Tensor, dtype: torch.dtype):
     y, d = torch.empty_like(x), torch.empty_like(x)
     check(lib.ssak_debug_gelu(ptr(x), x.numel(), ptr(y), ptr(d), 0 if dtype == torch.bfloat16 else 1, stream()))
     return y, d
+
+
+# ------------------------------------------------------------------ test-only: the grouped positional convolution (ABI 550)
+def debug_posconv_prepare(g: torch.Tensor, v: torch.Tensor, G: int, dtype: torch.dtype = torch.bfloat16):
+    """``k_posconv_prepare_t``: g [K], v [H, cg, K] fp32 -> (wf [H, K, cg], wb [G, cg, K, cg], norms); norms[:K] = ||v_k||^2, the
+    rest is the scratch ``debug_posconv_weight_bwd`` needs.  Outputs start from NaN."""
+    H, cg, K = v.shape
+    nan = float("nan")
+    wf = torch.full((H, K, cg), nan, dtype=dtype, device=v.device)
+    wb = torch.full((G, cg, K, cg), nan, dtype=dtype, device=v.device)
+    norms = torch.full(((2 + H) * K,), nan, dtype=torch.float32, device=v.device)
+    check(lib.ssak_debug_posconv_prepare(ptr(g), ptr(v), ptr(wf), ptr(wb), ptr(norms), H, G, K, _row_dtype(wf), stream()))
+    return wf, wb, norms
+
+
+def debug_posconv_pack(h: torch.Tensor, B: int, F: int, G: int, K: int):
+    """``k_posconv_pack_t`` on h [B * F, H] (bf16 or fp32) -> the packed [G, K / 2 + B (F + K) + K, cg], written over NaN."""
+    H = h.shape[1]
+    pg = torch.full((G, K // 2 + B * (F + K) + K, H // G), float("nan"), dtype=h.dtype, device=h.device)
+    check(lib.ssak_debug_posconv_pack(ptr(h), ptr(pg), B, F, H, G, K, _row_dtype(h), stream()))
+    return pg
+
+
+def debug_posconv_workspace(B: int, F: int, H: int, G: int, K: int, device):
+    """A workspace for ``debug_posconv_direct`` / ``debug_posconv_wgrad``, every byte 0xFF (NaN as bf16 and as fp32)."""
+    nbytes = lib.ssak_debug_posconv_workspace_bytes(B, F, H, G, K)
+    return torch.full((max(int(nbytes), 16),), 0xFF, dtype=torch.uint8, device=device)
+
+
+def debug_posconv_direct(h, w, bias, out, pre, B: int, F: int, G: int, K: int, *, row0=0, gelu=False, workspace=None):
+    """pack + fragment order + one ``k_posconv_direct`` launch into the caller's out / pre ([B * F, H] bf16; pre may be None).
+    w: bf16 in the wf layout [H, K, cg] (forward) or the wb layout [G, cg, K, cg] (input gradient, row0 = 1)."""
+    H = h.shape[1]
+    ws = workspace if workspace is not None else debug_posconv_workspace(B, F, H, G, K, h.device)
+    check(lib.ssak_debug_posconv_direct(ptr(h), ptr(w), ptr(bias), ptr(out), ptr(pre), B, F, H, G, K, int(row0), int(bool(gelu)),
+                                        ptr(ws), ws.numel(), stream()))
+
+
+def debug_posconv_wgrad(h, dpre, dwf, B: int, F: int, G: int, K: int, *, workspace=None):
+    """pack of both + ``k_posconv_wgrad_direct`` into dwf [G, K * cg, cg] fp32 (overwritten)."""
+    H = h.shape[1]
+    ws = workspace if workspace is not None else debug_posconv_workspace(B, F, H, G, K, h.device)
+    check(lib.ssak_debug_posconv_wgrad(ptr(h), ptr(dpre), ptr(dwf), B, F, H, G, K, ptr(ws), ws.numel(), stream()))
+
+
+def debug_posconv_weight_bwd(dwf, g, v, norms, dg, dv, G: int):
+    """``k_posconv_weight_bwd``: dg [K], dv [H, cg, K] += the weight-norm backward of dwf; norms from ``debug_posconv_prepare``."""
+    H, cg, K = v.shape
+    check(lib.ssak_debug_posconv_weight_bwd(ptr(dwf), ptr(g), ptr(v), ptr(norms), ptr(dg), ptr(dv), H, G, K, stream()))

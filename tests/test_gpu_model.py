@@ -419,7 +419,9 @@ def test_positional_conv_direct_kernel_equals_toeplitz_gemm(mods, geometry):
     (per-handle option SSAK_W2V2_OPT_POSCONV_DIRECT): same logits and the same gradients -- the positional convolution's own
     (weight_g / weight_v / bias) and everything upstream of it (feature projection), which only the input-gradient pass
     reaches -- to bf16 summation-order noise, on ragged utterances whose frame counts (499, 312, 77 / 150) exercise the edge tile, and
-    both against the CPU oracle at the usual bf16 bars."""
+    both against the CPU oracle at the usual bf16 bars.  (A whole-model check: the kernels themselves -- per element, per launch,
+    across the 512-frame tile and the weight gradient's stage and row-range boundaries -- are held to float64 by
+    tests/test_gpu_posconv.py.)"""
     import ssak_amd.hip as hip
     Wav2Vec2Config, Wav2Vec2ForCTC, R = mods
     if geometry == "base_cg48":
