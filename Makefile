@@ -7,15 +7,14 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := ssak_amd/csrc
-# (DEV objects in their own directory: a release build after a DEV build must not link objects that read the environment)
-OBJ ?= build/obj$(if $(DEV),_dev,)
+OBJ ?= build/obj
 LIB ?= ssak_amd/lib/libssak_hip.so
 # experiment builds next to the product: make OBJ=build/obj_x LIB=tools/ab_x.so EXTRA=-DSOME_VARIANT
 EXTRA ?=
-# `make DEV=1`: development switches read from the environment (SSAK_GEMM_P8, SSAK_ATTN_TILE, ...) are compiled in; the
-# release library has none (common.h: SSAK_DEV_ENV)
-DEVFLAGS := $(if $(DEV),-DSSAK_DEV,)
-HIPFLAGS := $(DEVFLAGS) $(EXTRA) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-lambda-capture -Iinclude -ffp-contract=fast -mllvm -amdgpu-mfma-vgpr-form -mllvm -amdgpu-atomic-optimizer-strategy=None
+# (The library reads nothing from the environment.  The development switches of earlier rounds and their `make DEV=1` build were
+# retired after commit 1fc4c62, the last to have them; the A/B numbers in DESIGN.md and profiles/ that name a switch were taken
+# with them.  A variant is now an EXTRA= build, as above.)
+HIPFLAGS := $(EXTRA) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-lambda-capture -Iinclude -ffp-contract=fast -mllvm -amdgpu-mfma-vgpr-form -mllvm -amdgpu-atomic-optimizer-strategy=None
 SRCS := $(wildcard $(CSRC)/*.hip) $(wildcard $(CSRC)/*.cpp)
 OBJS := $(patsubst $(CSRC)/%,$(OBJ)/%.o,$(SRCS))
 

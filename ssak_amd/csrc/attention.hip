@@ -18,18 +18,18 @@
 // word >= thresh16 << 16 -- one integer multiply, one compare and one select per score element; the forward and both
 // backward kernels regenerate identical masks.  Key-padding masks (ragged batches) are applied as -inf before the
 // softmax, as create_bidirectional_mask does.
-#include <cstdio>
-#include <cstdlib>
 #include <utility>
 
 #include "kernels.h"
 
 namespace {
 
-int attn_tile(int which);  // 16-row sub-tiles per wave: 0 forward (queries), 1 dQ kernel (queries), 2 dK/dV kernel (keys)
-
 constexpr int HD = 64;    // head dim
 constexpr int KT = 64;    // keys (or queries in dkv) per streamed tile
+// 16-row sub-tiles per wave in all three kernels (queries in the forward and dQ kernels, keys in the dK/dV kernel): a workgroup
+// covers 64 * TILE frames.  (One sub-tile per wave -- less state per wave, more waves in their VALU phase at once -- was measured
+// and lost to its extra LDS reads: DESIGN.md.)
+constexpr int TILE = 2;
 constexpr int TILE_BYTES = KT * HD * 2;  // 8 KiB
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4_t;
@@ -886,19 +886,6 @@ AttnParams make_params(const bf16* qkv, bf16* ctx, float* lse, const int32_t* kl
   return p;
 }
 
-// Per-wave tile of the three kernels (SSAK_ATTN_TILE="f,q,k", each 1 or 2; development switch).  The kernels are bound by
-// how many waves per SIMD are in their VALU phase at once (tools/probes/valu_rate.hip: one wave issues a VALU instruction
-// every ~6 cycles, the SIMD takes one every 3-4), so the smaller per-wave state of a 16-row tile can pay for its extra LDS reads.
-int attn_tile(int which) {
-  static int t[3] = {-1, -1, -1};
-  if (t[0] < 0) {
-    int v[3] = {2, 2, 2};
-    if (const char* e = SSAK_DEV_ENV("SSAK_ATTN_TILE")) sscanf(e, "%d,%d,%d", &v[0], &v[1], &v[2]);
-    for (int i = 0; i < 3; ++i) t[i] = v[i] == 1 ? 1 : 2;
-  }
-  return t[which];
-}
-
 }  // namespace
 
 bool k_attention_supported(int H, int nh) { return nh > 0 && H / nh == HD && H % nh == 0; }
@@ -909,32 +896,23 @@ int k_attention_fwd(const bf16* qkv, bf16* ctx, float* lse, const int32_t* klens
   SSAK_REQUIRE((long)F * 3 * H * 2 < 2000000000L, "attention: one utterance of q|k|v must span < 2 GB");
   const AttnParams p = make_params(qkv, ctx, lse, klens, nullptr, nullptr, nullptr, B, F, nh, H, drop);
   ProfScope prof_scope(PROF_ATTN_FWD, 4.0 * B * nh * (double)F * F * HD, st);  // S = Q K^T and O = P V
-  const int nqs = attn_tile(0);
   SSAK_REQUIRE(!p.thresh16 || F <= DROP_TABLE_N, "attention: dropout is built for at most %d frames", DROP_TABLE_N);
   const int cm_lds = p.thresh16 ? ssak_cdiv(F, KT) * KT * 4 : 0;  // the keys' dropout multipliers behind the tiles
   static bool fwd_attr_done = false;
   if (!fwd_attr_done) {
-    SSAK_HIP(hipFuncSetAttribute((const void*)attn_fwd_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * TILE_BYTES + DROP_TABLE_N * 4));
     SSAK_HIP(hipFuncSetAttribute((const void*)attn_fwd_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * TILE_BYTES + DROP_TABLE_N * 4));
     fwd_attr_done = true;
   }
-#define ATT_LAUNCH_FWD(D, N) attn_fwd_kernel<D, N><<<dim3(ssak_cdiv(F, 64 * N), nh, B), 256, 2 * 2 * TILE_BYTES + cm_lds, st>>>(p)
-  if (p.thresh16) {
-    if (nqs == 1) ATT_LAUNCH_FWD(true, 1); else ATT_LAUNCH_FWD(true, 2);
-  } else {
-    if (nqs == 1) ATT_LAUNCH_FWD(false, 1); else ATT_LAUNCH_FWD(false, 2);
-  }
+#define ATT_LAUNCH_FWD(D) attn_fwd_kernel<D, TILE><<<dim3(ssak_cdiv(F, 64 * TILE), nh, B), 256, 2 * 2 * TILE_BYTES + cm_lds, st>>>(p)
+  if (p.thresh16) ATT_LAUNCH_FWD(true); else ATT_LAUNCH_FWD(false);
 #undef ATT_LAUNCH_FWD
   SSAK_LAUNCH_CHECK();
   return SSAK_OK;
 }
 
 size_t k_attention_bwd_bias_floats(int B, int F, int H) {
-  // the bias partials need the two kernels to cut the frames into the same blocks (they do unless the development switch says otherwise)
-#ifdef SSAK_AB_NO_ATTN_BIAS  // A/B build: the separate column-sum pass of rounds 1-3
-  return 0;
-#endif
-  return attn_tile(1) == attn_tile(2) ? (size_t)B * ssak_cdiv(F, 64 * attn_tile(1)) * 3 * H : 0;
+  // one slot per block of frames: the dQ and the dK/dV kernel cut the frames into the same blocks
+  return (size_t)B * ssak_cdiv(F, 64 * TILE) * 3 * H;
 }
 
 int k_attention_bwd(const bf16* qkv, const bf16* ctx, const float* lse, const int32_t* klens, const bf16* dctx, float* delta,
@@ -943,51 +921,40 @@ int k_attention_bwd(const bf16* qkv, const bf16* ctx, const float* lse, const in
   SSAK_REQUIRE(k_attention_supported(H, nh), "attention: fused kernels are built for head_dim 64 (got %d)", nh ? H / nh : 0);
   SSAK_REQUIRE(mode == SSAK_ATTN_BWD_DEFAULT || mode == SSAK_ATTN_BWD_TWO_KERNEL,
                "attention_bwd: mode %d (0 / 1 = two kernels; the single-pass form, 2, was removed in ABI 400)", mode);
-  SSAK_REQUIRE(!bias_part == !bias_grad && (!bias_part || k_attention_bwd_bias_floats(B, F, H) > 0), "attention_bwd: bias partials need both pointers and equal block sizes");
+  SSAK_REQUIRE(!bias_part == !bias_grad, "attention_bwd: bias partials need both pointers");
   AttnParams p = make_params(qkv, const_cast<bf16*>(ctx), const_cast<float*>(lse), klens, dctx, delta, dqkv, B, F, nh, H, drop);
   p.bias_part = bias_part;
   ProfScope prof_scope(PROF_ATTN_BWD, 8.0 * B * nh * (double)F * F * HD, st);  // dV, dP, dQ, dK (the recomputed S is not algorithmic work)
-  const int nqs = attn_tile(1), nks = attn_tile(2);
   SSAK_REQUIRE(!p.thresh16 || F <= DROP_TABLE_N, "attention: dropout is built for at most %d frames", DROP_TABLE_N);
   const int cm_lds = p.thresh16 ? ssak_cdiv(F, KT) * KT * 4 : 0;  // the keys' dropout multipliers behind the tiles
   static bool dq_attr_done = false;
   if (!dq_attr_done) {
-    SSAK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * TILE_BYTES + DROP_TABLE_N * 4));
     SSAK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * TILE_BYTES + DROP_TABLE_N * 4));
     dq_attr_done = true;
   }
-#define ATT_LAUNCH_DQ(D, N) attn_bwd_dq_kernel<D, N><<<dim3(ssak_cdiv(F, 64 * N), nh, B), 256, 2 * 2 * TILE_BYTES + cm_lds, st>>>(p)
-  if (p.thresh16) {
-    if (nqs == 1) ATT_LAUNCH_DQ(true, 1); else ATT_LAUNCH_DQ(true, 2);
-  } else {
-    if (nqs == 1) ATT_LAUNCH_DQ(false, 1); else ATT_LAUNCH_DQ(false, 2);
-  }
+#define ATT_LAUNCH_DQ(D) attn_bwd_dq_kernel<D, TILE><<<dim3(ssak_cdiv(F, 64 * TILE), nh, B), 256, 2 * 2 * TILE_BYTES + cm_lds, st>>>(p)
+  if (p.thresh16) ATT_LAUNCH_DQ(true); else ATT_LAUNCH_DQ(false);
 #undef ATT_LAUNCH_DQ
   SSAK_LAUNCH_CHECK();
   constexpr int dkv_lds = 2 * 2 * TILE_BYTES + 2 * 3 * KT * 4;
   static bool attr_done = false;
   if (!attr_done) {
-#define ATT_DKV_ATTR(D, N, K) SSAK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<D, N, K>, hipFuncAttributeMaxDynamicSharedMemorySize, dkv_lds))
-    ATT_DKV_ATTR(true, 1, true); ATT_DKV_ATTR(false, 1, true); ATT_DKV_ATTR(true, 2, true); ATT_DKV_ATTR(false, 2, true);
-    ATT_DKV_ATTR(true, 1, false); ATT_DKV_ATTR(false, 1, false); ATT_DKV_ATTR(true, 2, false); ATT_DKV_ATTR(false, 2, false);
+#define ATT_DKV_ATTR(D, K) SSAK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<D, TILE, K>, hipFuncAttributeMaxDynamicSharedMemorySize, dkv_lds))
+    ATT_DKV_ATTR(true, true); ATT_DKV_ATTR(false, true); ATT_DKV_ATTR(true, false); ATT_DKV_ATTR(false, false);
 #undef ATT_DKV_ATTR
     attr_done = true;
   }
-#define ATT_LAUNCH_DKV(D, N)                                                                                        \
-  do {                                                                                                              \
-    if (klens) attn_bwd_dkv_kernel<D, N, true><<<dim3(ssak_cdiv(F, 64 * N), nh, B), 256, dkv_lds, st>>>(p);        \
-    else attn_bwd_dkv_kernel<D, N, false><<<dim3(ssak_cdiv(F, 64 * N), nh, B), 256, dkv_lds, st>>>(p);             \
+#define ATT_LAUNCH_DKV(D)                                                                                             \
+  do {                                                                                                                \
+    if (klens) attn_bwd_dkv_kernel<D, TILE, true><<<dim3(ssak_cdiv(F, 64 * TILE), nh, B), 256, dkv_lds, st>>>(p);    \
+    else attn_bwd_dkv_kernel<D, TILE, false><<<dim3(ssak_cdiv(F, 64 * TILE), nh, B), 256, dkv_lds, st>>>(p);         \
   } while (0)
-  if (p.thresh16) {
-    if (nks == 1) ATT_LAUNCH_DKV(true, 1); else ATT_LAUNCH_DKV(true, 2);
-  } else {
-    if (nks == 1) ATT_LAUNCH_DKV(false, 1); else ATT_LAUNCH_DKV(false, 2);
-  }
+  if (p.thresh16) ATT_LAUNCH_DKV(true); else ATT_LAUNCH_DKV(false);
 #undef ATT_LAUNCH_DKV
   SSAK_LAUNCH_CHECK();
   if (bias_part) {
     // second stage: with the caller's queued reductions (ReduceSink) when there is one, else here
-    const int slots = B * ssak_cdiv(F, 64 * nqs);
+    const int slots = B * ssak_cdiv(F, 64 * TILE);
     if (!(g_reduce_sink && g_reduce_sink->push(bias_part, 3L * H, slots, 3 * H, bias_grad))) {
       const int rc = k_colsum_rows(bias_part, slots, 3 * H, bias_grad, st);
       if (rc != SSAK_OK) return rc;
@@ -1032,11 +999,6 @@ extern "C" int ssak_attention_bwd_bias(const void* qkv, const void* ctx, const f
   d.p = drop_p;
   d.seed = seed;
   d.stream = stream_id;
-  if (k_attention_bwd_bias_floats(B, F, H) == 0) {  // (development switch SSAK_ATTN_TILE with unequal blocks)
-    const int rc = k_attention_bwd((const bf16*)qkv, (const bf16*)ctx, lse, klens, (const bf16*)dctx, delta, (bf16*)dqkv, B, F, nh, H, d,
-                                   SSAK_ATTN_BWD_DEFAULT, (hipStream_t)stream);
-    return rc != SSAK_OK ? rc : k_colsum((const bf16*)dqkv, 3L * H, B * F, 3 * H, bias_grad, (hipStream_t)stream);
-  }
   return k_attention_bwd((const bf16*)qkv, (const bf16*)ctx, lse, klens, (const bf16*)dctx, delta, (bf16*)dqkv, B, F, nh, H, d,
                          SSAK_ATTN_BWD_DEFAULT, (hipStream_t)stream, (float*)workspace, bias_grad);
 }

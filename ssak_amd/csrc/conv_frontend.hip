@@ -19,6 +19,8 @@ namespace {
 constexpr int KS0 = 10, ST0 = 5;  // conv0 taps / stride
 constexpr int FR_STATS = 1024, FR_APPLY = 128;  // frames per workgroup (statistics pass: few, contended fp64 atomics)
 
+// (Only the APPLY form is instantiated.  The other form left per-workgroup (sum y, sum y^2) partials of the convolution's output
+// for GroupNorm; the statistics now come from the input's moments in closed form: conv0_moments_kernel below.)
 template <typename OT, bool APPLY, int FR0>
 __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ x,
           a += red[l * nq + q][j];
           c += red[l * nq + q][4 + j];
         }
-        // per-workgroup partial; conv0_stats_finalize_kernel sums them in a fixed order
+        // per-workgroup partial, for a second pass that sums them in a fixed order
         double* dst = stats + (((size_t)b * gridDim.x + blockIdx.x) * C + q * 4 + j) * 2;
         dst[0] = a;
         dst[1] = c;
@@ -439,21 +441,6 @@ __global__ __launch_bounds__(256) void conv0_channel_stats_kernel(const double* 
   const double m = s1 / T0;
   sums[((size_t)b * C + c) * 2] = m;
   sums[((size_t)b * C + c) * 2 + 1] = 1.0 / sqrt(fmax(s2 / T0 - m * m, 0.0) + eps);
-}
-
-__global__ void conv0_stats_finalize_kernel(const double* __restrict__ partial, int nblk, int C, int T0, double* __restrict__ sums) {
-  // grid (ceil(C/256), B): sums[b][c] = (mean, 1 / sqrt(var + 1e-5)) from the nblk workgroup partials (sum y, sum y^2), fixed order
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const int b = blockIdx.y;
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = 0; k < nblk; ++k) {
-    s1 += partial[(((size_t)b * nblk + k) * C + c) * 2];
-    s2 += partial[(((size_t)b * nblk + k) * C + c) * 2 + 1];
-  }
-  const double m = s1 / T0;
-  sums[((size_t)b * C + c) * 2] = m;
-  sums[((size_t)b * C + c) * 2 + 1] = 1.0 / sqrt(fmax(s2 / T0 - m * m, 0.0) + 1e-5);
 }
 
 // ---- feature-encoder backward (--no_freeze, ssak/train/transformers/wav2vec_train.py:326-327 off) -------------------
@@ -814,7 +801,8 @@ int k_conv0_wgrad_t(const DT* d, const float* x, float* dw, float* scratch, int 
 }
 
 size_t k_conv0_stats_doubles(int B, int T0, int C) {
-  // [B][C] (mean, rstd) | per-workgroup partials: 2C (convolution-pass statistics) or NMOM (input moments) doubles each
+  // [B][C] (mean, rstd) | per-workgroup partials of NMOM input moments.  (The slots keep the larger of that and the 2C doubles an
+  // earlier statistics pass needed: callers size workspaces by this, and it is only the same number for C >= 36.)
   return (size_t)B * 2 * C + (size_t)B * ssak_cdiv(T0, FR_STATS) * std::max(2 * C, NMOM);
 }
 
@@ -824,27 +812,18 @@ int k_conv0_gn_gelu_t(const float* x, const float* w, const float* gamma, const 
   SSAK_REQUIRE(ksize == KS0 && stride == ST0, "conv0: only kernel 10 / stride 5 is built (got %d/%d)", ksize, stride);
   SSAK_REQUIRE((C & 3) == 0 && C <= 1024 && 256 % (C / 4) == 0, "conv0: C=%d must divide into 256 threads as quads", C);
   SSAK_REQUIRE(T0 == (T - KS0) / ST0 + 1 && T0 > 0, "conv0: T0 mismatch");
-  // stats layout: [B][C] (mean, rstd) | [B][nblk][2C] per-workgroup partials   (k_conv0_stats_doubles(B, T0, C) doubles)
+  // stats layout: [B][C] (mean, rstd) | [B][nblk][NMOM] per-workgroup partials   (within k_conv0_stats_doubles(B, T0, C) doubles)
   const int nblk = ssak_cdiv(T0, FR_STATS);
   ProfScope prof_scope(PROF_CONV0, (double)B * ((double)T * 4.0 + (double)T0 * C * sizeof(OT)), st);  // waveform in, channels-last out
   double* sums = stats;
   double* partial = stats + (size_t)B * 2 * C;
-  static const bool direct_stats = SSAK_DEV_ENV("SSAK_CONV0_DIRECT_STATS") != nullptr;  // development: the convolution-pass statistics
-  SSAK_REQUIRE(!(raw_input && direct_stats), "conv0: the folded normalisation needs the moment statistics");
-  if (direct_stats) {
-    conv0_kernel<OT, false, FR_STATS><<<dim3(nblk, B), 256, 0, st>>>(x, w, gamma, beta, out, partial, nullptr, T, T0, C);
-    SSAK_LAUNCH_CHECK();
-    conv0_stats_finalize_kernel<<<dim3(ssak_cdiv(C, 256), B), 256, 0, st>>>(partial, nblk, C, T0, sums);
-    SSAK_LAUNCH_CHECK();
-  } else {  // 65 input moments per utterance, then the channels' sums in closed form (NMOM <= 2 C doubles per partial slot)
-    conv0_moments_kernel<<<dim3(nblk, B), 256, 0, st>>>(x, T, T0, partial);
-    SSAK_LAUNCH_CHECK();
-    conv0_channel_stats_kernel<<<dim3(ssak_cdiv(C, 256), B), 256, 0, st>>>(partial, nblk, w, C, sums, T, T0, raw_input ? 1 : 0);
-    SSAK_LAUNCH_CHECK();
-  }
-  static const bool no_mfma = SSAK_DEV_ENV("SSAK_CONV0_VALU") != nullptr;  // development: the VALU apply pass
+  // the input's moments per utterance, then the channels' sums in closed form
+  conv0_moments_kernel<<<dim3(nblk, B), 256, 0, st>>>(x, T, T0, partial);
+  SSAK_LAUNCH_CHECK();
+  conv0_channel_stats_kernel<<<dim3(ssak_cdiv(C, 256), B), 256, 0, st>>>(partial, nblk, w, C, sums, T, T0, raw_input ? 1 : 0);
+  SSAK_LAUNCH_CHECK();
   if constexpr (sizeof(OT) == 2) {
-    if (C == 512 && !no_mfma) {
+    if (C == 512) {
       conv0_mfma_kernel<<<dim3(ssak_cdiv(T0, C0M_FR * C0M_SUB), B), 256, 0, st>>>(x, w, gamma, beta, (bf16*)out, sums, T, T0);
       SSAK_LAUNCH_CHECK();
       return SSAK_OK;

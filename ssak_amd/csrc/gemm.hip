@@ -13,8 +13,6 @@
 // 16x16x32 bf16 MFMAs.  The MFMA is issued with the operands swapped so each lane ends up with 4
 // consecutive output columns (8-/16-byte stores).  Workgroup ids are remapped so that each XCD's L2 sees a
 // contiguous run of tiles sharing the same A row panel.
-#include <stdlib.h>
-
 #include <algorithm>
 #include <vector>
 
@@ -630,7 +628,6 @@ __global__ void splitk_reduce_kernel(const GemmParams p) {
   }
 }
 
-bool g_no_big_tile = false;  // development switch (SSAK_GEMM_NO_BIG=1): keep the 128x128 kernels
 template <int BM, int BN, int WM, int WN, bool A_KM, bool B_KM, int NJ = 0>
 int launch(const GemmParams& p, bool dma, hipStream_t st) {
   const size_t lds = dma ? 2 * (size_t)(BM + BN) * 128 : 2 * (size_t)(Tile<BM, A_KM>::BYTES + Tile<BN, B_KM>::BYTES);
@@ -659,10 +656,10 @@ int launch(const GemmParams& p, bool dma, hipStream_t st) {
   return SSAK_OK;
 }
 
-template <bool A_KM, bool B_KM>
+// (K-contiguous operands only: the one layout the dispatch sends here)
 int launch_big(const GemmParams& p, hipStream_t st) {
   constexpr size_t lds = 3 * (size_t)(256 + 128) * 128;  // 144 KiB
-  auto kern = gemm_dma3_kernel<256, 128, 4, 2, A_KM, B_KM>;
+  auto kern = gemm_dma3_kernel<256, 128, 4, 2, false, false>;
   static bool attr_done = false;
   if (!attr_done) {
     SSAK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -670,22 +667,11 @@ int launch_big(const GemmParams& p, hipStream_t st) {
   }
   const long nblk = (long)p.tiles_m * p.tiles_n * p.nz * p.split_k;
   static int slot = -1;
-  if (slot < 0) {
-    char nm[112];
-    snprintf(nm, sizeof(nm), "gemm_dma3_kernel<256, 128, 4, 2, %s, %s>", A_KM ? "true" : "false", B_KM ? "true" : "false");
-    slot = ssak_prof_register(nm, SSAK_BOUND_MFMA);
-  }
+  if (slot < 0) slot = ssak_prof_register("gemm_dma3_kernel<256, 128, 4, 2, false, false>", SSAK_BOUND_MFMA);
   ProfScope prof_scope(slot, 2.0 * p.M * p.N * (double)p.K * p.nz, st);
   kern<<<dim3((unsigned)nblk), 512, lds, st>>>(p);
   SSAK_LAUNCH_CHECK();
   return SSAK_OK;
-}
-
-int dispatch_big(const GemmParams& p, int a_km, int b_km, hipStream_t st) {
-  if (!a_km && !b_km) return launch_big<false, false>(p, st);
-  if (!a_km && b_km) return launch_big<false, true>(p, st);
-  if (a_km && b_km) return launch_big<true, true>(p, st);
-  return launch_big<true, false>(p, st);
 }
 
 template <int BM, int BN, int WM, int WN, int NJ = 0>
@@ -729,17 +715,7 @@ struct GemmPlan {
   int split;
   double cost;
 };
-int g_env_p8 = -2, g_env_p8_bm = 0;
-bool g_no_p4 = false;  // development switch SSAK_GEMM_NO_P4: keep everything on the 8-wave kernel
 GemmPlan plan_gemm(const ssak_gemm_desc* d, bool dma, size_t workspace_bytes) {
-  if (g_env_p8 == -2) {
-    const char* v = SSAK_DEV_ENV("SSAK_GEMM_P8");  // development switches: 0 = never, 1 = whenever it applies
-    g_env_p8 = v ? atoi(v) : -1;
-    v = SSAK_DEV_ENV("SSAK_GEMM_P8_BM");
-    g_env_p8_bm = v ? atoi(v) : 0;
-    v = SSAK_DEV_ENV("SSAK_GEMM_NO_P4");
-    g_no_p4 = v && v[0] == '1';
-  }
   const int nkt = ssak_cdiv(d->K, BK);
   const long nz = (long)d->nb1 * d->nb2;
   const double out_mb = (double)nz * d->M * d->N * 4e-6;  // one fp32 slab, MB
@@ -753,7 +729,7 @@ GemmPlan plan_gemm(const ssak_gemm_desc* d, bool dma, size_t workspace_bytes) {
   // the 128 x 128 kernels, whose LDS-staged epilogue handles every mode)
   const bool p8_layout_ok = (d->epilogue != SSAK_EPI_GELU_SAVE_GRAD || (!d->a_kmajor && !d->b_kmajor)) &&
                             (d->epilogue != SSAK_EPI_MUL_AUX || !d->a_kmajor);
-  const bool p8_ok = dma && d->M >= 256 && d->N >= 256 && g_env_p8 != 0 && p8_layout_ok;
+  const bool p8_ok = dma && d->M >= 256 && d->N >= 256 && p8_layout_ok;
   if (p8_ok && (d->plan_tile == 256 || d->plan_tile == 192 || d->plan_tile == 128))
     return GemmPlan{true, d->plan_tile, s_lo, 0.0};  // caller's choice
   GemmPlan best_def{false, 0, s_lo, 1e30}, best_p8{true, 256, s_lo, 1e30};
@@ -768,14 +744,13 @@ GemmPlan plan_gemm(const ssak_gemm_desc* d, bool dma, size_t workspace_bytes) {
       if (c < best_def.cost) best_def = GemmPlan{false, 0, s, c};
     }
     for (int bm = 256; p8_ok && bm >= 128; bm -= 64) {
-      if (g_env_p8_bm && bm != g_env_p8_bm) continue;
       const long blocks = (long)ssak_cdiv(d->M, bm) * ssak_cdiv(d->N, 256) * nz * s;
       const double epi = ((slab || wide) ? 9.4 : 4.7) * bm / 256.0;
       const double c = (double)ssak_cdiv(blocks, 256) * (2.0 + epi + kt * (0.60 + 0.98 * bm / 256.0)) + reduce;
       if (c < best_p8.cost) best_p8 = GemmPlan{true, bm, s, c};
     }
   }
-  if (p8_ok && best_p8.cost < 1e30 && (g_env_p8 == 1 || best_p8.cost < 0.97 * best_def.cost)) return best_p8;
+  if (best_p8.cost < 0.97 * best_def.cost) return best_p8;
   return best_def;
 }
 
@@ -793,14 +768,37 @@ bool fragments_pay(const ssak_gemm_desc* d, const GemmPlan& plan) {
   return false;
 }
 
+// What the kernels need to know about one product's operands, and the requirements on them that every entry point shares
+// (`who` prefixes the messages; nullptr: derive only -- ssak_gemm_uses_fragments asks before there are operands).
+struct GemmOperands {
+  bool dma;               // the LDS-DMA kernels cannot mask partial 16-byte chunks: they need whole chunks or zero padding in memory
+  bool fits;              // kernels address an operand slice with 32-bit byte offsets from its (batch-adjusted) base: < 2 GB
+  uint32_t ext_a, ext_b;  // bytes of one slice, rounded up to whole 16-byte chunks: a partial last chunk is still fetched (ld* and
+                          // the allocation cover it)
+};
+int gemm_operands(const char* who, const ssak_gemm_desc& d, const void* A, const void* B, const void* C, GemmOperands* o) {
+  if (who) {
+    SSAK_REQUIRE((d.lda & 7) == 0 && (d.ldb & 7) == 0 && (d.ldc & 3) == 0, "%s: lda/ldb must be multiples of 8, ldc of 4", who);
+    SSAK_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 && ((uintptr_t)C & 15) == 0, "%s: operands must be 16-byte aligned", who);
+  }
+  const bool partial_a = d.a_kmajor ? (d.M & 7) : (d.K & 7);
+  const bool partial_b = d.b_kmajor ? (d.N & 7) : (d.K & 7);
+  o->dma = d.pads_are_zero || !(partial_a || partial_b);
+  const double ext_a = d.a_kmajor ? ((double)(d.K - 1) * d.lda + d.M) : ((double)(d.M - 1) * d.lda + d.K);
+  const double ext_b = d.b_kmajor ? ((double)(d.K - 1) * d.ldb + d.N) : ((double)(d.N - 1) * d.ldb + d.K);
+  o->fits = ext_a * 2 < 2.0e9 && ext_b * 2 < 2.0e9;
+  o->ext_a = o->fits ? (uint32_t)(((long)ext_a + 7) / 8 * 16) : 0;
+  o->ext_b = o->fits ? (uint32_t)(((long)ext_b + 7) / 8 * 16) : 0;
+  return SSAK_OK;
+}
+
 }  // namespace
 
 extern "C" int ssak_gemm_uses_fragments(const ssak_gemm_desc* d) {
   if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
-  const bool partial_a = d->a_kmajor ? (d->M & 7) : (d->K & 7);
-  const bool partial_b = d->b_kmajor ? (d->N & 7) : (d->K & 7);
-  const bool dma = d->pads_are_zero || !(partial_a || partial_b);
-  return fragments_pay(d, plan_gemm(d, dma, 0)) ? 1 : 0;
+  GemmOperands ops;
+  gemm_operands(nullptr, *d, nullptr, nullptr, nullptr, &ops);
+  return fragments_pay(d, plan_gemm(d, ops.dma, 0)) ? 1 : 0;
 }
 extern "C" size_t ssak_gemm_fragment_b_bytes(int N, int K) { return N > 0 && K > 0 ? k_gemm_fragment_b_bytes(N, K) : 0; }
 extern "C" int ssak_gemm_fragment_b_batched(int n, const void* const* B, const long* ldb, const int* N, const int* K, const int* b_kmajor,
@@ -818,8 +816,8 @@ extern "C" int ssak_gemm_bf16(const ssak_gemm_desc* d, const void* A, const void
                               void* stream) {
   SSAK_REQUIRE(d && A && B && C, "gemm: null pointer");
   SSAK_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "gemm: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
-  SSAK_REQUIRE((d->lda & 7) == 0 && (d->ldb & 7) == 0 && (d->ldc & 3) == 0, "gemm: lda/ldb must be multiples of 8, ldc of 4");
-  SSAK_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 && ((uintptr_t)C & 15) == 0, "gemm: operands must be 16-byte aligned");
+  GemmOperands ops;
+  if (const int rc = gemm_operands("gemm", *d, A, B, C, &ops); rc != SSAK_OK) return rc;
   SSAK_REQUIRE(((d->sa1 | d->sa2 | d->sb1 | d->sb2) & 7) == 0 && ((d->sc1 | d->sc2) & 3) == 0 &&
                    !(d->drop_p > 0.f && ((d->sc1 | d->sc2 | d->ldc) & 3)), "gemm: batch strides must keep 16-byte (A,B) / 8-byte (C) alignment");
   SSAK_REQUIRE(d->nb1 > 0 && d->nb2 > 0, "gemm: batch counts must be >= 1");
@@ -828,17 +826,10 @@ extern "C" int ssak_gemm_bf16(const ssak_gemm_desc* d, const void* A, const void
   SSAK_REQUIRE(!d->accumulate || d->out_f32, "gemm: accumulate needs fp32 output");
   SSAK_REQUIRE(d->split_k >= 0, "gemm: split_k must be >= 0 (0 = choose)");
   SSAK_REQUIRE(d->split_k <= 1 || d->epilogue == SSAK_EPI_NONE, "gemm: split_k supports the plain epilogue only");
-  // the LDS-DMA kernels cannot mask partial 16-byte chunks: they need whole chunks or zero padding in memory
-  const bool partial_a = d->a_kmajor ? (d->M & 7) : (d->K & 7);
-  const bool partial_b = d->b_kmajor ? (d->N & 7) : (d->K & 7);
-  const bool dma = d->pads_are_zero || !(partial_a || partial_b);
-  const GemmPlan plan = plan_gemm(d, dma, workspace ? workspace_bytes : 0);
-  const int split = plan.split;
-  static const bool env_trace = SSAK_DEV_ENV("SSAK_GEMM_TRACE") != nullptr;  // development: one line per launch
-  if (env_trace)
-    fprintf(stderr, "gemm M=%d N=%d K=%d akm=%d bkm=%d nb=%dx%d epi=%d f32=%d acc=%d drop=%g dma=%d -> %s bm=%d split=%d cost=%.1f\n", d->M,
-            d->N, d->K, d->a_kmajor, d->b_kmajor, d->nb1, d->nb2, d->epilogue, d->out_f32, d->accumulate, d->drop_p, (int)dma,
-            plan.p8 ? "p8" : "tile128", plan.bm, plan.split, plan.cost);
+  const GemmPlan plan = plan_gemm(d, ops.dma, workspace ? workspace_bytes : 0);
+  const bool dma = ops.dma;
+  const int split = plan.split, p8_bm = plan.bm;
+  const int nz = d->nb1 * d->nb2, nkt = ssak_cdiv(d->K, BK);
   // column sums of C (desc.colsum): fused into the LDS-free epilogue of the 256-wide kernel when every tile takes it,
   // otherwise a separate pass over the stored bf16 C
   float* colsum_out = nullptr;
@@ -851,6 +842,13 @@ extern "C" int ssak_gemm_bf16(const ssak_gemm_desc* d, const void* A, const void
     colsum_fused = plan.p8 && plan.split == 1 && (d->N % 256) == 0 && (d->ldc & 7) == 0 && workspace &&
                    workspace_bytes >= (size_t)ssak_cdiv(d->M, 64) * d->N * sizeof(float);
   }
+  SSAK_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "gemm: drop_p must be in [0,1)");
+  SSAK_REQUIRE(!(d->drop_p > 0.f && d->split_k > 1), "gemm: dropout epilogue is not available with split_k");
+  SSAK_REQUIRE(!(d->drop_p > 0.f) || d->N <= DROP_TABLE_N, "gemm: the dropout epilogue is built for at most %d output columns", DROP_TABLE_N);
+  if (split > 1)
+    SSAK_REQUIRE(workspace && workspace_bytes >= (size_t)split * nz * (size_t)d->M * d->N * sizeof(float),
+                 "gemm: split_k workspace too small");
+  SSAK_REQUIRE(ops.fits, "gemm: one batch slice of an operand must span < 2 GB");
   GemmParams p;
   p.A = (const bf16*)A;
   p.B = (const bf16*)B;
@@ -878,7 +876,8 @@ extern "C" int ssak_gemm_bf16(const ssak_gemm_desc* d, const void* A, const void
   p.accumulate = d->accumulate;
   p.dynamic = d->dynamic_tiles;
   p.split_k = split;
-  p.nz = d->nb1 * d->nb2;
+  p.nz = nz;
+  p.kt_per_split = ssak_cdiv(nkt, split);
   // 16-bit dropout uniforms in the epilogue: threshold = round(p * 65536), scale from the realised keep probability
   p.drop_thresh = d->drop_p > 0.f ? (uint32_t)fminf(65535.f, roundf(d->drop_p * 65536.f)) : 0u;
   p.drop_scale = p.drop_thresh ? 1.f / (1.f - (float)p.drop_thresh / 65536.f) : 1.f;
@@ -892,44 +891,19 @@ extern "C" int ssak_gemm_bf16(const ssak_gemm_desc* d, const void* A, const void
     p.drop_thresh = 0;
   }
   p.bias_s2 = d->bias_s2;
-  p.colsum = nullptr;
-  SSAK_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "gemm: drop_p must be in [0,1)");
-  SSAK_REQUIRE(!(d->drop_p > 0.f && d->split_k > 1), "gemm: dropout epilogue is not available with split_k");
-  SSAK_REQUIRE(!(d->drop_p > 0.f) || d->N <= DROP_TABLE_N, "gemm: the dropout epilogue is built for at most %d output columns", DROP_TABLE_N);
-  const int nkt = ssak_cdiv(d->K, BK);
-  p.kt_per_split = ssak_cdiv(nkt, split);
-  if (split > 1)
-    SSAK_REQUIRE(workspace && workspace_bytes >= (size_t)split * p.nz * (size_t)d->M * d->N * sizeof(float),
-                 "gemm: split_k workspace too small");
-  {
-    // kernels address an operand slice with 32-bit byte offsets from its (batch-adjusted) base
-    const double ext_a = d->a_kmajor ? ((double)(d->K - 1) * d->lda + d->M) : ((double)(d->M - 1) * d->lda + d->K);
-    const double ext_b = d->b_kmajor ? ((double)(d->K - 1) * d->ldb + d->N) : ((double)(d->N - 1) * d->ldb + d->K);
-    SSAK_REQUIRE(ext_a * 2 < 2.0e9 && ext_b * 2 < 2.0e9, "gemm: one batch slice of an operand must span < 2 GB");
-    // round up to whole 16-byte chunks: a partial last chunk is still fetched (ld* and the allocation cover it)
-    p.ext_a = (uint32_t)(((long)ext_a + 7) / 8 * 16);
-    p.ext_b = (uint32_t)(((long)ext_b + 7) / 8 * 16);
-  }
+  p.ext_a = ops.ext_a;
+  p.ext_b = ops.ext_b;
+  p.colsum = colsum_fused ? (float*)workspace : nullptr;
+  p.kperm_p = p.kperm_n2 = 0;
+  // (tiles_m / tiles_n, and for the persistent kernel the K order and the fragment image of B, follow from the kernel chosen below)
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  static const bool env_no_big = [] {
-    const char* nb = SSAK_DEV_ENV("SSAK_GEMM_NO_BIG");
-    return nb && nb[0] == '1';
-  }();
-  const long big_tiles = (long)ssak_cdiv(d->M, 256) * ssak_cdiv(d->N, 128) * p.nz * split;
-  const int p8_bm = plan.bm;
-  if (colsum_fused) p.colsum = (float*)workspace;
-  p.kperm_p = p.kperm_n2 = 0;
   if (plan.p8) {
     p.tiles_m = ssak_cdiv(d->M, p8_bm);
     p.tiles_n = ssak_cdiv(d->N, 256);
     // Toeplitz A (conv as GEMM, rows overlap: lda < K): visit the K tiles so that the two reads of the same bytes -- tap t + s of
     // row i is tap t of row i + 1 -- are one K step apart instead of lda / BK steps (gemm_common.h: kperm_*)
-    static const bool env_no_perm = [] {
-      const char* e = SSAK_DEV_ENV("SSAK_GEMM_NO_KPERM");
-      return e && e[0] == '1';
-    }();
-    if (!d->a_kmajor && split == 1 && d->K % BK == 0 && d->lda % BK == 0 && d->lda < d->K && !env_no_perm) {
+    if (!d->a_kmajor && split == 1 && d->K % BK == 0 && d->lda % BK == 0 && d->lda < d->K) {
       const int pp = (int)(d->lda / BK), n2 = nkt - pp;
       if (n2 > 0 && n2 <= pp) {
         p.kperm_p = pp;
@@ -941,32 +915,32 @@ extern "C" int ssak_gemm_bf16(const ssak_gemm_desc* d, const void* A, const void
       p.B = (const bf16*)d->b_fragments;
       p.ext_b = (uint32_t)k_gemm_fragment_b_bytes(d->N, d->K);
       rc = ssak_gemm_p8bd_launch(&p, p8_bm, st);
-    } else if (!g_no_p4 && ssak_gemm_p4_supports(&p, p8_bm, d->a_kmajor, d->b_kmajor)) {
+    } else if (ssak_gemm_p4_supports(&p, p8_bm, d->a_kmajor, d->b_kmajor)) {
       rc = ssak_gemm_p4_launch(&p, p8_bm, d->b_kmajor, st);
     } else {
       rc = ssak_gemm_p8_launch(&p, p8_bm, d->a_kmajor, d->b_kmajor, st);
     }
-  } else if (d->N > 64 && dma && d->M >= 256 && !d->a_kmajor && !d->b_kmajor && big_tiles >= 2048 && !env_no_big && !g_no_big_tile) {
+  } else if (d->N > 64 && dma && d->M >= 256 && !d->a_kmajor && !d->b_kmajor &&
+             (long)ssak_cdiv(d->M, 256) * ssak_cdiv(d->N, 128) * nz * split >= 2048) {
     p.tiles_m = ssak_cdiv(d->M, 256);
     p.tiles_n = ssak_cdiv(d->N, 128);
-    rc = dispatch_big(p, d->a_kmajor, d->b_kmajor, st);
+    rc = launch_big(p, st);
   } else if (d->N > 64) {
     p.tiles_m = ssak_cdiv(d->M, 128);
     p.tiles_n = ssak_cdiv(d->N, 128);
     rc = dispatch_layout<128, 128, 2, 2>(p, d->a_kmajor, d->b_kmajor, dma, st);
+  } else if (dma && d->N > 32 && d->N <= 48 && d->M >= 256 && !d->a_kmajor && !d->b_kmajor) {
+    // K-contiguous operands: 256-row tiles -- twice the MFMA work per K step behind the same LDS-DMA round trip (this two-stage
+    // kernel is latency-bound): 437 -> 378 us per step for the three forward / dX launches.  (K-major operands, the weight
+    // gradient: 250 -> 325 us, so they stay on 128 rows.)
+    // (512-row tiles, one workgroup per CU: 576 us)
+    p.tiles_m = ssak_cdiv(d->M, 256);
+    p.tiles_n = ssak_cdiv(d->N, 64);
+    rc = launch<256, 64, 4, 1, false, false, 3>(p, dma, st);
   } else {
     p.tiles_m = ssak_cdiv(d->M, 128);
     p.tiles_n = ssak_cdiv(d->N, 64);
-    static const bool env_no_n48 = SSAK_DEV_ENV("SSAK_GEMM_NO_N48") != nullptr;  // development switches
-    static const bool env_n48_128 = SSAK_DEV_ENV("SSAK_GEMM_N48_128") != nullptr;
-    if (dma && d->N > 32 && d->N <= 48 && !env_no_n48 && !env_n48_128 && d->M >= 256 && !d->a_kmajor && !d->b_kmajor) {
-      // K-contiguous operands: 256-row tiles -- twice the MFMA work per K step behind the same LDS-DMA round trip (this two-stage
-      // kernel is latency-bound): 437 -> 378 us per step for the three forward / dX launches.  (K-major operands, the weight
-      // gradient: 250 -> 325 us, so they stay on 128 rows.)
-      // (512-row tiles, one workgroup per CU: 576 us)
-      p.tiles_m = ssak_cdiv(d->M, 256);
-      rc = launch<256, 64, 4, 1, false, false, 3>(p, dma, st);
-    } else if (dma && d->N > 32 && d->N <= 48 && !env_no_n48)
+    if (dma && d->N > 32 && d->N <= 48)
       rc = dispatch_layout<128, 64, 4, 1, 3>(p, d->a_kmajor, d->b_kmajor, dma, st);  // N = 48 (grouped positional conv): no padding MFMAs
     else
       rc = dispatch_layout<128, 64, 2, 2>(p, d->a_kmajor, d->b_kmajor, dma, st);
@@ -1013,18 +987,13 @@ extern "C" int ssak_gemm_bf16_grouped(const ssak_gemm_desc* descs, int n, const 
                      d.accumulate == d0.accumulate, "gemm_grouped: layouts, alpha and output type must match");
     SSAK_REQUIRE(d.nb1 == 1 && d.nb2 == 1 && d.epilogue == SSAK_EPI_NONE && !(d.drop_p > 0.f) && d.split_k <= 1,
                  "gemm_grouped: plain single products only");
-    SSAK_REQUIRE((d.lda & 7) == 0 && (d.ldb & 7) == 0 && (d.ldc & 3) == 0, "gemm_grouped: lda/ldb must be multiples of 8, ldc of 4");
-    SSAK_REQUIRE(((uintptr_t)A[i] & 15) == 0 && ((uintptr_t)B[i] & 15) == 0 && ((uintptr_t)C[i] & 15) == 0,
-                 "gemm_grouped: operands must be 16-byte aligned");
+    GemmOperands ops;
+    if (const int rc = gemm_operands("gemm_grouped", d, A[i], B[i], C[i], &ops); rc != SSAK_OK) return rc;
     SSAK_REQUIRE(!d.accumulate || d.out_f32, "gemm_grouped: accumulate needs fp32 output");
-    const bool partial_a = d.a_kmajor ? (d.M & 7) : (d.K & 7);
-    const bool partial_b = d.b_kmajor ? (d.N & 7) : (d.K & 7);
-    SSAK_REQUIRE(d.pads_are_zero || !(partial_a || partial_b), "gemm_grouped: operands need whole 16-byte chunks (or zero padding)");
-    const double xa = d.a_kmajor ? ((double)(d.K - 1) * d.lda + d.M) : ((double)(d.M - 1) * d.lda + d.K);
-    const double xb = d.b_kmajor ? ((double)(d.K - 1) * d.ldb + d.N) : ((double)(d.N - 1) * d.ldb + d.K);
-    SSAK_REQUIRE(xa * 2 < 2.0e9 && xb * 2 < 2.0e9, "gemm_grouped: an operand must span < 2 GB");
-    ea[i] = (uint32_t)(((long)xa + 7) / 8 * 16);
-    eb[i] = (uint32_t)(((long)xb + 7) / 8 * 16);
+    SSAK_REQUIRE(ops.dma, "gemm_grouped: operands need whole 16-byte chunks (or zero padding)");
+    SSAK_REQUIRE(ops.fits, "gemm_grouped: an operand must span < 2 GB");
+    ea[i] = ops.ext_a;
+    eb[i] = ops.ext_b;
     Ms[i] = d.M;
     Ns[i] = d.N;
     lda[i] = d.lda;

@@ -24,12 +24,8 @@
 
 namespace {
 
-constexpr int WGRAD_SETS = 12;  // most buffer sets of the queued weight-gradient operands = layers per grouped launch (4 products each: ssak_gemm_bf16_grouped takes 48)
-bool wgrad_all() {
-  static const bool v = SSAK_DEV_ENV("SSAK_WGRAD_ALL") != nullptr;  // development switch: see the workspace plan
-  return v;
-}
-
+// buffer sets of the queued weight-gradient operands (three: a layer's last product may wait for the launch after next)
+constexpr int WGRAD_SETS = 3;
 
 struct PInfo {
   std::string name;
@@ -68,10 +64,8 @@ struct Plan {
   // backward temporaries
   size_t dlog, dA, dB, dY, dC, dI, dqkv, dSb, pgdy, dwf, slab, dln0, scratchH, lnpart, redring, redring_floats;
   // sets of the buffers the weight-gradient products read (dy of both LayerNorms, dI, dqkv): those products are queued and
-  // launched several layers at a time (two under data parallelism, up to WGRAD_SETS on a single GPU), so a layer's set
-  // must survive the backward of the layers queued after it
+  // launched several layers at a time, so a layer's set must survive the backward of the layers queued after it
   size_t dY1 = 0, dYb[WGRAD_SETS] = {0}, dIb[WGRAD_SETS] = {0}, dqkvb[WGRAD_SETS] = {0}, dY1b[WGRAD_SETS] = {0};
-  int wgrad_sets = 2;
   // Whisper front end: RS2 rows per utterance after conv2, RS1 = 2*RS2 before it
   int Tin = 0, RS1 = 0, RS2 = 0;
   bool fused_attn = false;
@@ -436,11 +430,10 @@ int make_plan(const ssak_w2v2* e, int B, int T, int training, Plan& p) {
     p.dY1b[0] = p.dY1;
     p.dIb[0] = p.dI;
     p.dqkvb[0] = p.dqkv;
-    // two sets (layer pairs) by default; SSAK_WGRAD_ALL=1: up to WGRAD_SETS layers per grouped launch on a single GPU -- measured
-    // SLOWER (eleven layers as one 1 188-tile launch: 2 064 us per step against 2 014 us in pairs, the same 0.46 of the roof per
-    // tile: the better fill of the rounds is lost again to the operand panels of many layers competing for the L2)
-    p.wgrad_sets = wgrad_all() ? std::max(2, std::min(WGRAD_SETS, c.num_layers)) : 3;  // (three: a layer's last product may wait for the launch after next)
-    for (int s2 = 1; s2 < p.wgrad_sets; ++s2) {
+    // (a set per layer and all kept layers in one grouped launch was measured SLOWER on a single GPU -- eleven layers as one
+    // 1 188-tile launch: 2 064 us per step against 2 014 us in pairs, the same 0.46 of the roof per tile: the better fill of the
+    // rounds is lost again to the operand panels of many layers competing for the L2)
+    for (int s2 = 1; s2 < WGRAD_SETS; ++s2) {
       p.dYb[s2] = cv.take((size_t)M * H * b2);
       p.dY1b[s2] = cv.take((size_t)M * H * b2);
       p.dIb[s2] = cv.take((size_t)M * I * b2);
@@ -579,10 +572,10 @@ struct GemmX : Gemm {
 // queue is packed greedily into launches of at most one round of 256 x 256 tiles (see flush_gemms in the backward): ~2.4 base
 // layers per launch (rounds 1-2: pairs of layers, 216 tiles, with the odd layer LayerDrop leaves over as four split-K
 // launches); under data parallelism a layer's gradient range is announced for the bucketed all-reduce as soon as its last
-// product has been launched.  All kept layers in one multi-round launch (SSAK_WGRAD_ALL=1; 1 188 tiles for eleven layers = 4.6
-// rounds) was measured slower on one GPU: see the plan.
+// product has been launched.  All kept layers in one multi-round launch (1 188 tiles for eleven layers = 4.6 rounds) was
+// measured slower on one GPU: see the plan.
 struct WgradQueue {
-  static constexpr int CAP = 4 * WGRAD_SETS;  // four products per encoder layer
+  static constexpr int CAP = 48;  // what ssak_gemm_bf16_grouped takes in one launch
   ssak_gemm_desc d[CAP];
   const void* A[CAP];
   const void* B[CAP];
@@ -1396,7 +1389,7 @@ static int backward_impl(ssak_w2v2* e, const float* dlogits, const bf16* dhidden
     return SSAK_OK;
   };
   auto wq_push = [&](const Gemm& g, int buffer_set) -> int {
-    const bool full = !wgrad_all() && wq.tiles + WgradQueue::tiles_of(g.d) > 256;  // (SSAK_WGRAD_ALL: multi-round launches on purpose)
+    const bool full = wq.tiles + WgradQueue::tiles_of(g.d) > 256;
     if (wq.n > 0 && (full || wq.n == WgradQueue::CAP)) TRY(flush_gemms());
     wq.push(g, buffer_set);
     return SSAK_OK;
@@ -1450,7 +1443,7 @@ static int backward_impl(ssak_w2v2* e, const float* dlogits, const bf16* dhidden
     const size_t qkv_fused_floats = (p.fused_attn && !EXACT) ? k_attention_bwd_bias_floats(B, F, H) : 0;
     TRY(red_get(std::max((size_t)64 * 3 * H, qkv_fused_floats), &qkv_part));
     AT* dR = stable ? free_buf(gA, gB, Gres) : BF(p.dC);  // grad wrt r2
-    const int set = kept % p.wgrad_sets;
+    const int set = kept % WGRAD_SETS;
     ++kept;
     if (wq.uses_set(set)) TRY(flush_gemms());  // a queued product still reads the buffers this layer is about to overwrite
     AT* dY = BF(p.dYb[set]);     // dy of the feed-forward branch (dropout mask applied): dX and dW operand
@@ -1519,10 +1512,7 @@ static int backward_impl(ssak_w2v2* e, const float* dlogits, const bf16* dhidden
     wq.ann_cnt[wq.n_ann] = layer_span;
     wq.ann_last[wq.n_ann++] = wq.pushed - 1;  // announced once the qkv product -- the layer's last -- has been launched
     ++wq.layers;
-    if (wgrad_all() ? (wq.layers % p.wgrad_sets == 0) : false)
-      TRY(flush_wgrads());  // (SSAK_WGRAD_ALL: one launch per p.wgrad_sets layers)
-    else if ((wq.layers & 1) == 0)
-      TRY(flush_reductions());  // the deferred second stages of the column reductions go out every two layers
+    if ((wq.layers & 1) == 0) TRY(flush_reductions());  // the deferred second stages of the column reductions go out every two layers
     if (!stable) {
       // gradient w.r.t. this layer's input = dR1 (residual of r1) + dX
       gA = dR1;
@@ -1580,8 +1570,7 @@ static int backward_impl(ssak_w2v2* e, const float* dlogits, const bf16* dhidden
     // (37 % useful) and this product was the slowest launch of the backward
     bool pcw_direct = false;
     if constexpr (!EXACT)
-      pcw_direct = e->posconv_direct && e->pc_wf_frag != nullptr && k_posconv_wgrad_scratch_floats(H, G, K) * sizeof(float) <= p.slab_bytes &&
-                   !SSAK_DEV_ENV("SSAK_PCW_GEMM");  // (development builds: the weight gradient alone as the Toeplitz GEMM, tools/pcw_check.py)
+      pcw_direct = e->posconv_direct && e->pc_wf_frag != nullptr && k_posconv_wgrad_scratch_floats(H, G, K) * sizeof(float) <= p.slab_bytes;
     if (pcw_direct) {
       // direct contraction over time: a stage of x and dy rows is written to LDS once and serves every tap (posconv.hip)
       if constexpr (!EXACT)

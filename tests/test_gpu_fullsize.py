@@ -237,7 +237,7 @@ def test_base_matched_loss_50_steps_vs_hf_curve(gold, which):
       through gradient-norm spikes of 166.  Through the descent (steps 0-12) the curves must agree to 5e-3 per step (measured:
       1.3e-3); on the plateau the fp32 reference itself scatters by +-2 % from step to step (its gradient norm jumps between 2
       and 12) and the trajectory is chaotic: replacing ONE weight-gradient kernel by another that agrees with it to 2e-7
-      relative (fp32 summation order; tests/dev_pcw_check.py) moves the largest per-step deviation from 1.8e-2 (step 26) to 5.4e-2
+      relative (fp32 summation order; a development build of commit 1fc4c62) moves the largest per-step deviation from 1.8e-2 (step 26) to 5.4e-2
       (step 17).  So there the per-step bar is 8e-2 and the bar that means something is 1e-2 on the means of 10-step windows."""
     from oracle import w2v2_ref as R
     from oracle.gen_golden_full import curve_inputs

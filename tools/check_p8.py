@@ -1,5 +1,6 @@
-"""Development check of the 256x256 phase-interleaved GEMM (run with SSAK_GEMM_P8=1): exact integer products on
-ragged shapes, all four layouts, K tails, split-K, batches; repeated to screen for LDS-DMA races."""
+"""Development check of the 256x256 phase-interleaved GEMM (plan_tile=256 takes every product to it, whatever the cost
+model would pick): exact integer products on ragged shapes, all four layouts, K tails, split-K; repeated to screen for
+LDS-DMA races."""
 import itertools
 import sys
 import torch
@@ -37,7 +38,7 @@ def one(M, N, K, a_km, b_km, split_k=1, reps=3):
     for _ in range(reps):
         Cc = torch.full((M, Np), -7.0, dtype=torch.float32).cuda()
         h.gemm(Ad, Bd, Cc, M, N, K, a_kmajor=a_km, b_kmajor=b_km, lda=A.shape[1], ldb=B.shape[1], ldc=Np, split_k=split_k,
-               pads_are_zero=True)
+               pads_are_zero=True, plan_tile=256)
         ok = torch.equal(Cc[:, :N], r) and bool((Cc[:, N:] == -7.0).all())
         bad += 0 if ok else 1
         if not ok:
