@@ -604,6 +604,24 @@ int ssak_augment_time_stretch(const float* x, const int32_t* lens, const int32_t
                               const double* params_host /*host*/, float* y, int32_t* out_lens, int T_out, void* workspace,
                               size_t workspace_bytes, void* stream);
 
+/* ---- augmentation of the SpeechBrain recipe (ABI 560): TimeDomainSpecAugment's DropFreq and DropChunk in one pass ---------
+ * Contract and draws: ssak_amd/augment.py (the project's own, modelled on speechbrain 0.5; parity with speechbrain's bits is
+ * unpinned).  The speed perturbation before it is ssak_resample_sinc on the padded batch.
+ *   out[b, t] = 0                                        if t lies in one of row b's chunks,
+ *             = sum_k taps[k] * x[b, t + k - ntaps / 2]   otherwise (zeros outside [0, T)): a CROSS-CORRELATION, as
+ *               torch.nn.functional.conv1d computes it, accumulated in fp32 (any order of the ntaps terms).
+ * x, out [B, T] fp32, any T >= 1; out must not overlap x.  taps [ntaps] fp32 on the device, ntaps odd and
+ * <= SSAK_AUG_FIR_MAX_TAPS; taps = NULL with ntaps = 0 means no filter (out = x outside the chunks, bit for bit).
+ * chunks [B, max_chunks, 2] int32 on the device: (start, end) of the half-open sample ranges to zero, clipped to [0, T) by the
+ * kernel; chunk_counts [B] int32 on the device and chunk_counts_host, the same counts in host memory (validated before any
+ * launch: 0 <= count <= max_chunks).  chunks = NULL: no chunk is dropped (the counts and max_chunks are then ignored).
+ * A workgroup produces SSAK_AUG_FIR_TILE consecutive outputs of one row from a tile plus halo held in LDS; needs no
+ * workspace. */
+#define SSAK_AUG_FIR_MAX_TAPS 255
+#define SSAK_AUG_FIR_TILE 2048
+int ssak_augment_fir_drop(const float* x, int B, int T, const float* taps, int ntaps, const int32_t* chunks, const int32_t* chunk_counts,
+                          const int32_t* chunk_counts_host /*host*/, int max_chunks, float* out, void* stream);
+
 /* ---- TEST-ONLY entries (not part of the product path; kept in the release library so that the parity tests run against the
  * library that ships): dropout bits of one site ------------------------------------------------------------------------
  * The engine stores no dropout mask: each site recomputes keep(seed, site, element) in its forward and backward kernels

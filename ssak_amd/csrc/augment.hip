@@ -577,6 +577,142 @@ extern "C" int ssak_augment_reverb(const float* x, const int32_t* lens, const in
 }
 
 namespace {
+// ------------------------------------------------------------------------------------------------ FIR + chunk drop
+// TimeDomainSpecAugment's DropFreq (one 101-tap notch product for the batch) and DropChunk in one read and one write of the
+// batch.  A workgroup makes FIR_TILE consecutive outputs of one row: the tile and its halo go to LDS once (16-byte loads
+// where the row allows them), each thread then makes two groups of 4 consecutive outputs from sliding register windows, so
+// that a step of 4 taps costs two 16-byte LDS reads of samples and one (broadcast) of taps for 32 FMAs.
+//
+// Alignment: rows start at b * T floats, which is 16-byte aligned for no T in particular, so the tiles of row b start at
+// t0 = tile * FIR_TILE - m with m = (b * T) mod 4: the flat index of every fourth sample of a tile, and of every thread's first
+// output, is then a multiple of 4.  The window is read from LDS at offsets that are multiples of 4 as well: LDS index j holds
+// row sample t0 - lead + j with lead = ntaps / 2 rounded up to 4, and the taps are stored behind s = lead - ntaps / 2 zeros.
+constexpr int FIR_TILE = SSAK_AUG_FIR_TILE, FIR_THREADS = 256, FIR_SUB = FIR_TILE / (4 * FIR_THREADS);
+constexpr int FIR_KP_MAX = (SSAK_AUG_FIR_MAX_TAPS + 3 + 3) / 4 * 4;  // taps behind <= 3 zeros, rounded up to 4: 260
+static_assert(FIR_SUB == 2, "fir_drop_kernel is written for two groups of 4 outputs per thread");
+
+// One 16-byte LDS read that stays one: left to itself the compiler fetches the window's odd pairs (the operands of its packed
+// FMAs) with separate 8-byte reads at odd offsets, 4 lanes to a bank.
+typedef float fir_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ fir_f4 lds16(const float4* p) {  // p points into LDS
+  return *(const volatile __attribute__((address_space(3))) fir_f4*)p;
+}
+
+// 4 samples of a row from sample r on (r + the row's base is a multiple of 4 when `wide`), zeros outside [0, T)
+__device__ __forceinline__ float4 load4(const float* __restrict__ xb, int r, int T, bool wide) {
+  if (wide && r >= 0 && r + 3 < T) return *(const float4*)(xb + r);
+  float4 v;
+  v.x = r >= 0 && r < T ? xb[r] : 0.f;
+  v.y = r + 1 >= 0 && r + 1 < T ? xb[r + 1] : 0.f;
+  v.z = r + 2 >= 0 && r + 2 < T ? xb[r + 2] : 0.f;
+  v.w = r + 3 >= 0 && r + 3 < T ? xb[r + 3] : 0.f;
+  return v;
+}
+
+// Thread i makes outputs 4 i .. 4 i + 3 of each half of the tile: consecutive lanes read consecutive 16-byte slots of LDS (no
+// bank conflict for 16-byte reads; 8 consecutive outputs per thread would put the lanes 32 bytes apart, 2 lanes per slot) and
+// store consecutive 16 bytes.
+__global__ __launch_bounds__(FIR_THREADS) void fir_drop_kernel(const float* __restrict__ x, int T, const float* __restrict__ taps, int ntaps,
+                                                               const int32_t* __restrict__ chunks, const int32_t* __restrict__ counts,
+                                                               int max_chunks, float* __restrict__ out, int wide) {
+  __shared__ float4 xs[(FIR_TILE + FIR_KP_MAX) / 4];
+  __shared__ float4 ts[FIR_KP_MAX / 4];
+  const int b = blockIdx.y;
+  const size_t base = (size_t)b * T;
+  const int m = wide ? (int)(base & 3) : 0;
+  const int t0 = blockIdx.x * FIR_TILE - m;
+  if (t0 >= T) return;
+  const float* xb = x + base;
+  float* ob = out + base;
+  const int32_t* ch = chunks ? chunks + (size_t)b * max_chunks * 2 : nullptr;
+  const int nch = chunks ? min(max(counts[b], 0), max_chunks) : 0;
+  float4 acc[FIR_SUB];
+  if (ntaps == 0) {  // no filter: a copy
+#pragma unroll
+    for (int h = 0; h < FIR_SUB; ++h) acc[h] = load4(xb, t0 + (h * FIR_THREADS + threadIdx.x) * 4, T, wide);
+  } else {
+    const int half = ntaps >> 1, lead = (half + 3) & ~3, s = lead - half;
+    const int kp = (s + ntaps + 3) & ~3;
+    for (int j = threadIdx.x; j < kp; j += FIR_THREADS) ((float*)ts)[j] = j >= s && j - s < ntaps ? taps[j - s] : 0.f;
+    for (int j4 = threadIdx.x; j4 < (FIR_TILE + kp) / 4; j4 += FIR_THREADS) xs[j4] = load4(xb, t0 - lead + 4 * j4, T, wide);
+    __syncthreads();
+    const float4* win0 = xs + threadIdx.x;
+    const float4* win1 = xs + FIR_THREADS + threadIdx.x;
+    fir_f4 a0 = lds16(win0), b0 = lds16(win1);
+    float ya[4] = {0.f, 0.f, 0.f, 0.f}, yb[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+    for (int k4 = 0; k4 < kp / 4; ++k4) {
+      const fir_f4 a1 = lds16(win0 + k4 + 1), b1 = lds16(win1 + k4 + 1);
+      const fir_f4 g = lds16(ts + k4);
+      const float wa[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+      const float wb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+      const float gg[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          ya[i] = fmaf(gg[j], wa[i + j], ya[i]);
+          yb[i] = fmaf(gg[j], wb[i + j], yb[i]);
+        }
+      a0 = a1;
+      b0 = b1;
+    }
+    acc[0] = make_float4(ya[0], ya[1], ya[2], ya[3]);
+    acc[1] = make_float4(yb[0], yb[1], yb[2], yb[3]);
+  }
+  float y[FIR_SUB][4] = {{acc[0].x, acc[0].y, acc[0].z, acc[0].w}, {acc[1].x, acc[1].y, acc[1].z, acc[1].w}};
+  for (int c = 0; c < nch; ++c) {
+    const int cs = ch[2 * c], ce = ch[2 * c + 1];
+    if (ce <= t0 || cs >= t0 + FIR_TILE) continue;  // (uniform: most tiles meet no chunk)
+#pragma unroll
+    for (int h = 0; h < FIR_SUB; ++h)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int t = t0 + (h * FIR_THREADS + threadIdx.x) * 4 + i;
+        if (t >= cs && t < ce) y[h][i] = 0.f;
+      }
+  }
+#pragma unroll
+  for (int h = 0; h < FIR_SUB; ++h) {
+    const int t = t0 + (h * FIR_THREADS + threadIdx.x) * 4;  // this thread's first output of this half
+    if (wide && t >= 0 && t + 4 <= T) {
+      *(float4*)(ob + t) = make_float4(y[h][0], y[h][1], y[h][2], y[h][3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (t + i >= 0 && t + i < T) ob[t + i] = y[h][i];
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int ssak_augment_fir_drop(const float* x, int B, int T, const float* taps, int ntaps, const int32_t* chunks,
+                                     const int32_t* chunk_counts, const int32_t* chunk_counts_host, int max_chunks, float* out, void* stream) {
+  SSAK_REQUIRE(x && out, "augment_fir_drop: null pointer");
+  SSAK_REQUIRE(B > 0 && B <= 65535 && T > 0 && T <= (1 << 30), "augment_fir_drop: bad shape B=%d T=%d", B, T);
+  SSAK_REQUIRE(out + (size_t)B * T <= x || x + (size_t)B * T <= out, "augment_fir_drop: out must not overlap x");
+  if (taps) {
+    SSAK_REQUIRE(ntaps > 0 && (ntaps & 1) && ntaps <= SSAK_AUG_FIR_MAX_TAPS, "augment_fir_drop: ntaps = %d must be odd and at most %d", ntaps,
+                 SSAK_AUG_FIR_MAX_TAPS);
+  } else {
+    SSAK_REQUIRE(ntaps == 0, "augment_fir_drop: null taps with ntaps = %d", ntaps);
+  }
+  if (chunks) {
+    SSAK_REQUIRE(chunk_counts && chunk_counts_host, "augment_fir_drop: chunks without their counts");
+    SSAK_REQUIRE(max_chunks > 0, "augment_fir_drop: max_chunks = %d", max_chunks);
+    for (int b = 0; b < B; ++b)
+      SSAK_REQUIRE(chunk_counts_host[b] >= 0 && chunk_counts_host[b] <= max_chunks, "augment_fir_drop: row %d has %d chunks, outside [0, %d]", b,
+                   chunk_counts_host[b], max_chunks);
+  }
+  const int wide = (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
+  fir_drop_kernel<<<dim3(ssak_cdiv((long)T + 3, FIR_TILE), B), FIR_THREADS, 0, (hipStream_t)stream>>>(x, T, taps, ntaps, chunks, chunk_counts,
+                                                                                                      max_chunks, out, wide);
+  SSAK_LAUNCH_CHECK();
+  return SSAK_OK;
+}
+
+namespace {
 void ts_sizes(int T, int T_out, int* fmax, int* omax) {
   *fmax = 1 + T / TS_HOP;
   *omax = (T_out + TS_NFFT + TS_HOP - 1) / TS_HOP;

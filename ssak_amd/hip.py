@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 550  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 560  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -66,6 +66,7 @@ AUG_NONE, AUG_GAIN, AUG_NOISE_MIX, AUG_REVERB = -1, 0, 1, 2
 (AUG_KIND, AUG_GAIN_DB, AUG_GAIN_LIN, AUG_SNR_DB, AUG_SNR_AMP, AUG_NOISE, AUG_NOISE_START, AUG_RIR, AUG_RIR_PEAK, AUG_RATE,
  AUG_OUT_LEN) = range(11)
 AUG_NCOL = 11
+AUG_FIR_MAX_TAPS, AUG_FIR_TILE = 255, 2048  # SSAK_AUG_FIR_MAX_TAPS, SSAK_AUG_FIR_TILE
 
 GRAD_READY_FN = C.CFUNCTYPE(None, C.c_long, C.c_long, C.c_void_p)
 
@@ -94,6 +95,7 @@ def _load():
         "ssak_augment_reverb": (i32, [vp, vp, vp, i32, i32, vp, vp, C.POINTER(AudioBank), vp, vp, sz, vp]),
         "ssak_augment_time_stretch_workspace_bytes": (sz, [i32, i32, i32]),
         "ssak_augment_time_stretch": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, sz, vp]),
+        "ssak_augment_fir_drop": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp]),
         "ssak_ctc_lm_beam_workspace_bytes": (sz, [i32, i32, i32, i32]),
         "ssak_ctc_lm_beam_decode": (i32, [vp, vp, i32, i32, i32, C.POINTER(NgramLMDesc), C.POINTER(LMBeamParams), vp, vp, vp,
                                           vp, sz, vp]),
@@ -366,6 +368,30 @@ def augment_time_stretch(x, lens, lens_host, params, params_host, T_out: int, wo
     check(lib.ssak_augment_time_stretch(ptr(x), ptr(lens), _hp(lens_host), B, T, ptr(params), _hp(params_host), ptr(y), ptr(out_lens),
                                         int(T_out), ptr(ws), ws.numel(), stream()))
     return y, out_lens
+
+
+def augment_fir_drop(x, taps=None, chunks=None, chunk_counts=None, chunk_counts_host=None, out=None):
+    """``ssak_augment_fir_drop``: x [B,T] fp32 cross-correlated with ``taps`` [ntaps] (device fp32, odd length; None: no filter), the
+    samples of ``chunks`` [B, max_chunks, 2] int32 (start, end; ``chunk_counts`` [B] int32 of them per row, on the device and,
+    ``chunk_counts_host``, as a host array) set to 0 -> out [B,T], which must not be x."""
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2
+    B, T = x.shape
+    out = torch.empty_like(x) if out is None else out
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape
+    ntaps = 0
+    if taps is not None:
+        assert taps.dtype == torch.float32 and taps.is_contiguous() and taps.dim() == 1
+        ntaps = taps.numel()
+    max_chunks, counts_h = 0, None
+    if chunks is not None:
+        assert chunks.dtype == torch.int32 and chunks.is_contiguous() and chunks.dim() == 3 and chunks.shape[0] == B and chunks.shape[2] == 2
+        assert chunk_counts.dtype == torch.int32 and chunk_counts.is_contiguous() and chunk_counts.shape == (B,)
+        counts_h = np.ascontiguousarray(chunk_counts_host, dtype=np.int32)
+        assert counts_h.shape == (B,)
+        max_chunks = chunks.shape[1]
+    check(lib.ssak_augment_fir_drop(ptr(x), B, T, ptr(taps), ntaps, ptr(chunks), ptr(chunk_counts), None if counts_h is None else _hp(counts_h),
+                                    max_chunks, ptr(out), stream()))
+    return out
 
 
 def lm_query(lm: NgramLMDesc, ctx_ids: torch.Tensor, words: torch.Tensor):

@@ -5,13 +5,25 @@
 ``HPARAMS.yaml`` is the recipe's own file (``ssak/train/speechbrain/fr/hyperparameters_wav2vec_finetune_cv-fr.yaml``): its
 scalar entries (num_epochs, lr, lr_wav2vec, batch_size, test_batch_size, min/max_duration, freeze_wav2vec, eval_steps, seed,
 sorting, dnn_neurons, output_neurons, blank_index ...) and the NewBob / Adadelta blocks are read with a tag-tolerant YAML
-loader (hyperpyyaml itself is not installed: ``!new:`` / ``!name:`` nodes are taken as plain mappings, ``!ref <key>`` is
-resolved for scalars, ``!PLACEHOLDER`` must come from the command line) and every ``--key=value`` overrides an entry, as
+loader (hyperpyyaml itself is not installed: ``!new:`` / ``!name:`` nodes are taken as mappings that remember their tag,
+``!ref <key>`` is resolved for scalars, ``!PLACEHOLDER`` must come from the command line) and every ``--key=value`` overrides an entry, as
 ``sb.parse_arguments`` does.  What the objects of the yaml stand for is built by ``ssak_amd.sb_head`` (Brain, CTCHead,
 Adadelta, NewBobScheduler).  Differences, all on the host side of the path: ``base_model`` is a HuggingFace-layout wav2vec2
 folder (speechbrain checkpoints cannot be read without speechbrain), the tokenizer is the character set of the training
-text with index 0 = blank (the recipe trains a SentencePiece "char" model of ``output_neurons`` pieces on the same text),
-``TimeDomainSpecAugment`` is not applied.
+text with index 0 = blank (the recipe trains a SentencePiece "char" model of ``output_neurons`` pieces on the same text).
+
+``augmentation`` (wav2vec_train.py:45-46: training batches only) is applied on the device, before ``fit_batch``, and the
+relative lengths are recomputed from the augmented ones; validation batches are never augmented:
+``!new:speechbrain.lobes.augment.TimeDomainSpecAugment`` (the finetune yaml) builds ``augment.TimeDomainSpecAugmentDevice``
+from the mapping's keys -- the project's own contract modelled on speechbrain 0.5, parity with speechbrain's bits unpinned:
+the speed change uses this project's resampler (torchaudio's formula, not speechbrain's Kaldi-style filter) and dropped
+chunks are placed by absolute lengths (ssak_amd/augment.py); ``!new:ssak.utils.augment.SpeechAugment`` (the from-scratch
+yaml) builds the ``SpeechAugmentDevice`` of ``train --data_augment`` from ``noise_dir``, ``rir_dir`` and ``rir_lists``, which
+augments every utterance: ``apply_prob`` is not honoured and must be given as 1; no entry, ``null`` or
+``--augmentation=none`` trains on clean audio; any other class is an error.  Draws are keyed by (seed, global step, position
+in the global batch), so they do not depend on the world size and a resumed run needs no extra state.
+``--valid_before_training=true`` (this command line's own key, off by default) logs one validation pass before the first step
+of a new run as an ``epoch: 0`` line of ``train_log.txt``.
 
 Output folder (``<output_folder_prefix>sb_<md5 of data>_...``): ``train_log.txt`` (one line per validation, the recipe's
 fields), ``save/CKPT-<step>/`` (head, optimizers, schedulers, wav2vec2 when unfrozen; the two best by WER are kept, as
@@ -41,9 +53,21 @@ class _Loader(yaml.SafeLoader):
     pass
 
 
+class Tagged(dict):
+    """The mapping of a ``!new:`` / ``!name:`` node; ``tag`` keeps what followed the ``!`` (``new:pkg.Class``).  Equal to the
+    plain dict of its entries."""
+    tag = ""
+
+    @property
+    def class_name(self) -> str:
+        return self.tag.split(":", 1)[1] if ":" in self.tag else self.tag
+
+
 def _tagged(loader, suffix, node):
     if isinstance(node, yaml.MappingNode):
-        return loader.construct_mapping(node, deep=True)
+        m = Tagged(loader.construct_mapping(node, deep=True))
+        m.tag = suffix
+        return m
     if isinstance(node, yaml.SequenceNode):
         return loader.construct_sequence(node, deep=True)
     v = loader.construct_scalar(node)
@@ -79,7 +103,11 @@ def load_hparams(path: str, overrides: Dict[str, str]) -> dict:
                 return resolve(hp.get(m.group(1)), depth + 1)
             return re.sub(r"<([A-Za-z0-9_]+)>", lambda mm: str(resolve(hp.get(mm.group(1)), depth + 1)), expr)
         if isinstance(v, dict):
-            return {k: resolve(x, depth) for k, x in v.items()}
+            out = {k: resolve(x, depth) for k, x in v.items()}
+            if isinstance(v, Tagged):
+                out = Tagged(out)
+                out.tag = v.tag
+            return out
         return v
 
     hp = {k: resolve(v) for k, v in hp.items()}
@@ -87,6 +115,51 @@ def load_hparams(path: str, overrides: Dict[str, str]) -> dict:
     if missing:
         raise SystemExit(f"mandatory entries without a value: {', '.join('--' + k for k in missing)}")
     return hp
+
+
+TDSA_CLASSES = ("speechbrain.lobes.augment.TimeDomainSpecAugment", "speechbrain.augment.time_domain.TimeDomainSpecAugment")
+SPEECH_AUGMENT_CLASS = "ssak.utils.augment.SpeechAugment"
+
+
+def select_augmentation(hp: dict, seed: int = 1234):
+    """The ``augmentation`` entry of the hyper-parameters -> None (absent, ``null``, ``none``) or (class, keyword arguments) of
+    the device augmentation that stands for it (module docstring); host only, nothing is loaded.  Raises ValueError for a
+    class or an argument this command line cannot honour."""
+    from .augment import SpeechAugmentDevice, TimeDomainSpecAugmentDevice
+    entry = hp.get("augmentation")
+    if entry is None or (isinstance(entry, str) and entry.strip().lower() in ("", "none", "null", "false")):
+        return None
+    name = entry.class_name if isinstance(entry, Tagged) else str(entry)
+    args = dict(entry) if isinstance(entry, dict) else {}
+    if name in TDSA_CLASSES:
+        import inspect
+        known = set(inspect.signature(TimeDomainSpecAugmentDevice.__init__).parameters) - {"self", "seed"}
+        unknown = sorted(set(args) - known)
+        if unknown:
+            raise ValueError(f"augmentation {name}: unknown argument(s) {', '.join(unknown)}")
+        args.setdefault("sample_rate", int(hp.get("sample_rate", 16000)))
+        args["seed"] = int(seed)
+        TimeDomainSpecAugmentDevice(**args)  # (validates the values; the instance that trains is built by the caller)
+        return TimeDomainSpecAugmentDevice, args
+    if name == SPEECH_AUGMENT_CLASS:
+        known = {"sample_rate", "noise_dir", "rir_dir", "rir_lists", "apply_prob", "verbose", "save_audio_dir"}
+        unknown = sorted(set(args) - known)
+        if unknown:
+            raise ValueError(f"augmentation {name}: argument(s) {', '.join(unknown)} are not supported here "
+                             "(speed and gain always; noise_dir, rir_dir and rir_lists as given)")
+        apply_prob = args.get("apply_prob", 0.5)  # (0.5 is the reference class's default, ssak/utils/augment.py:67)
+        if float(apply_prob) != 1.0:
+            raise ValueError(f"augmentation {name}: apply_prob = {apply_prob} is not honoured (every training utterance is augmented, as "
+                             "train --data_augment does): set apply_prob: 1")
+        if args.get("save_audio_dir"):
+            raise ValueError(f"augmentation {name}: save_audio_dir is not supported")
+        if bool(args.get("rir_dir")) != bool(args.get("rir_lists")):
+            raise ValueError(f"augmentation {name}: rir_dir and rir_lists go together")
+        rir_arg = "{}/[{}]".format(str(args["rir_dir"]).rstrip("/"), ",".join(args["rir_lists"])) if args.get("rir_dir") else None
+        return SpeechAugmentDevice, {"noise_dir": args.get("noise_dir") or None, "rir_arg": rir_arg,
+                                     "sample_rate": int(args.get("sample_rate", hp.get("sample_rate", 16000))), "seed": int(seed)}
+    raise ValueError(f"augmentation: class {name} is not supported (supported: {TDSA_CLASSES[0]}, {SPEECH_AUGMENT_CLASS}; "
+                     "--augmentation=none trains without)")
 
 
 def parse_argv(argv: List[str]):
@@ -190,6 +263,10 @@ def load_checkpoint(d, brain):
 def main(argv=None):
     hfile, overrides = parse_argv(list(sys.argv[1:] if argv is None else argv))
     hp = load_hparams(hfile, overrides)
+    try:
+        aug_spec = select_augmentation(hp, int(hp.get("seed", 1234)))
+    except ValueError as e:
+        raise SystemExit(str(e))
     if not hp.get("base_model") or not os.path.isdir(str(hp["base_model"])):
         raise SystemExit("--base_model must be a HuggingFace-layout wav2vec2 folder (config.json, model.safetensors, vocab.json)")
     from .checkpoint import load_pretrained
@@ -250,6 +327,21 @@ def main(argv=None):
             tot, n = tot + float(loss.item()) * len(idx), n + len(idx)
         return tot / max(n, 1)
 
+    augment = None
+    if aug_spec is not None:
+        from .augment import SpeechAugmentDevice
+        augment = aug_spec[0](**aug_spec[1], **({"device": dev} if aug_spec[0] is SpeechAugmentDevice else {}))
+        if rank == 0:
+            print(f"augmentation of training batches: {aug_spec[0].__name__}")
+
+    def augmented(step, positions, idx):
+        """The training batch of utterances ``idx`` (``positions`` in the global batch) augmented on the device."""
+        x, lens = pad_waves([tw[i] for i in idx])
+        table = augment.draw(step, positions, [int(n) for n in lens])
+        with torch.cuda.device(dev):
+            y, ylens = augment.apply(torch.from_numpy(x).to(dev), torch.from_numpy(lens.astype(np.int32)).to(dev), table)
+        return y, ylens.cpu().to(torch.float32) / y.shape[1]
+
     # resume (:625-640)
     state = {"step": 0, "epoch": 1, "total_samples": 0, "total_tokens": 0, "total_frames": 0, "train_time_h": 0.0, "valid_time_h": 0.0}
     cks = _ckpt_dirs(save_dir)
@@ -257,6 +349,12 @@ def main(argv=None):
         state.update(load_checkpoint(cks[-1], brain))
         if rank == 0:
             print(f"resuming from {cks[-1]} (step {state['step']})")
+    elif hp.get("valid_before_training"):
+        v0 = validate()
+        brain._wer = None  # (the pass takes no part in the schedulers or in the next validation's WER)
+        if rank == 0:
+            with open(os.path.join(out_dir, "train_log.txt"), "a") as f:
+                f.write(f"epoch: 0, epoch_finished: False, total_samples: 0 - valid loss: {v0:.4f}\n")
     step, t0 = 0, time.time()
     run_loss, run_n = 0.0, 0
     for epoch in range(1, num_epochs + 1):
@@ -280,6 +378,8 @@ def main(argv=None):
                 continue
             idx = gidx[rank:per * world:world] if world > 1 else gidx
             wavs, wl, toks, tl = batch_of(idx, tw, tt)
+            if augment is not None:
+                wavs, wl = augmented(step, range(rank, per * world, world) if world > 1 else range(len(idx)), idx)
             loss = brain.fit_batch(wavs, wl, toks, tl)
             run_loss, run_n = run_loss + float(loss.item()), run_n + 1
             state["total_samples"] += len(gidx)
