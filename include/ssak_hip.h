@@ -696,6 +696,44 @@ int ssak_debug_posconv_wgrad(const void* h, const void* dpre, float* dwf, int B,
 int ssak_debug_posconv_weight_bwd(const float* dwf, const float* g, const float* v, float* norms, float* dg, float* dv, int H, int G,
                                   int K, void* stream);
 
+/* ---- TEST-ONLY entries (ABI 570): the kernels that run only when the feature encoder trains (conv_frontend.hip) and the
+ * data movers of the Whisper front end (whisper_frontend.hip), one k_* launch function each -----------------------------
+ * dtype 0 = bf16 (the engine), 1 = fp32 (the fp32-exact mode) is the storage type of the void* activations; weights,
+ * waveforms and gradients of weights are fp32.  Shapes a kernel is not built for are SSAK_ERR_INVALID before any launch.
+ * conv0 = Conv1d(1, C, k = 10, s = 5): x [B, T] fp32, w [C][10], T0 = (T - 10) / 5 + 1 frames, activations [B, T0, C].
+ * conv0_bwd: backward of GELU(GroupNorm_C-groups(conv0(x)) gamma + beta) from dy [B, T0, C]; sums [B][C] (mean, rstd) doubles
+ *   as ssak_conv0_gn_gelu leaves them at the start of its workspace; dw [C][10], dgamma [C], dbeta [C] +=.  T >= 10, B <= 65535,
+ *   C a multiple of 4, C <= 1024 and C / 4 a divisor of 256; workspace (8-byte aligned) >= ssak_debug_conv0_bwd_workspace_bytes(B, T, C).
+ * conv0_wgrad: dw [C][ksize] += sum_{b,t} d[b, t, c] x[b, stride t + k], T0 = (T - ksize) / stride + 1 (ksize <= 10,
+ *   64 stride + ksize <= 336, C even and <= 512); workspace >= ssak_debug_conv0_wgrad_workspace_bytes(B, C, ksize).
+ * conv0_bias: out [B, T0, C] = conv0(x) + bias (bias may be NULL).  As for conv0_bwd: T >= 10, B <= 65535, C a multiple of 4,
+ *   C <= 1024 and C / 4 a divisor of 256.
+ * col2im: dx [B, Tin, C] = the input gradient of a channels-last Conv1d(k, s, no padding) from its column form dxcol
+ *   [B, Tout, k, C]: row u sums dxcol[t][kk] over u = t s + kk; rows no window reaches are 0.  C a multiple of 8.
+ * sum_slabs: out [n] = sum_b slabs[b][n], b = 0 .. nb - 1 in that order.
+ * conv_weight_rearrange: out[co][kk][ci] (dtype) = w[co][ci][kk];  conv_wgrad_unrearrange: g[co][ci][kk] += dwr[co][kk][ci].
+ * col2im_k3s2: out [B, RS1, H] = the input gradient of Conv1d(k = 3, s = 2, pad = 1) from dxcol [B, F, 3, H], F = (Tin + 1) / 2,
+ *   times gelu'(pre); pre [B * RS1, H] holds input row u of utterance b at row b RS1 + 1 + u; rows u >= Tin of out are 0.
+ *   RS1 > Tin, H a multiple of 8.
+ * mel_to_cl: cl[b RS + lead + t][c] (dtype) = mel[b][c][t], mel [B, C, T] fp32; other rows of cl are left alone.
+ * add_rowvec: out [B, F, H] = x + pos[t] (pos [F, H]);  copy_rows_padded: dst [B, RS, H] = src [B, F, H], rows >= F zero. */
+size_t ssak_debug_conv0_bwd_workspace_bytes(int B, int T, int C);
+int ssak_debug_conv0_bwd(const float* x, const float* w, const float* gamma, const float* beta, const void* dy, const double* sums,
+                         float* dw, float* dgamma, float* dbeta, int B, int T, int C, int dtype, void* workspace, size_t workspace_bytes,
+                         void* stream);
+size_t ssak_debug_conv0_wgrad_workspace_bytes(int B, int C, int ksize);
+int ssak_debug_conv0_wgrad(const void* d, const float* x, float* dw, int B, int T, int C, int ksize, int stride, int dtype, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int ssak_debug_conv0_bias(const float* x, const float* w, const float* bias, void* out, int B, int T, int C, int dtype, void* stream);
+int ssak_debug_col2im(const void* dxcol, void* dx, int B, int Tin, int Tout, int C, int k, int s, int dtype, void* stream);
+int ssak_debug_sum_slabs(const float* slabs, int nb, long n, float* out, void* stream);
+int ssak_debug_conv_weight_rearrange(const float* w, void* out, int Co, int Ci, int k, int dtype, void* stream);
+int ssak_debug_conv_wgrad_unrearrange(const float* dwr, float* g, int Co, int Ci, int k, void* stream);
+int ssak_debug_col2im_k3s2(const void* dxcol, const void* pre, void* out, int B, int F, int Tin, int RS1, int H, int dtype, void* stream);
+int ssak_debug_mel_to_cl(const float* mel, void* cl, int B, int C, int T, int RS, int lead, int dtype, void* stream);
+int ssak_debug_add_rowvec(const void* x, const void* pos, void* out, int B, int F, int H, int dtype, void* stream);
+int ssak_debug_copy_rows_padded(const void* src, void* dst, int B, int F, int RS, int H, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1014,3 +1014,84 @@ extern "C" int ssak_debug_posconv_weight_bwd(const float* dwf, const float* g, c
   SSAK_REQUIRE(pc_debug_shape(H, G, K), "debug_posconv_weight_bwd: H=%d G=%d K=%d", H, G, K);
   return k_posconv_weight_bwd(dwf, g, v, norms, dg, dv, H, G, K, (hipStream_t)stream);
 }
+
+// ---- debug: the kernels that run only when the feature encoder trains (--no_freeze), one launch function each
+// (tests/test_gpu_frontend.py; the Whisper front end's entries are in whisper_frontend.hip).  Nothing on the hot path calls these.
+namespace {
+bool c0_debug_shape(int B, int T, int C) { return B > 0 && B <= 65535 && T >= KS0 && (C & 3) == 0 && C > 0 && C <= 1024 && 256 % (C / 4) == 0; }
+}  // namespace
+
+extern "C" size_t ssak_debug_conv0_bwd_workspace_bytes(int B, int T, int C) {
+  if (!c0_debug_shape(B, T, C)) return 0;
+  return k_conv0_bwd_scratch_floats(B, (T - KS0) / ST0 + 1, C) * sizeof(float);
+}
+
+extern "C" int ssak_debug_conv0_bwd(const float* x, const float* w, const float* gamma, const float* beta, const void* dy,
+                                    const double* sums, float* dw, float* dgamma, float* dbeta, int B, int T, int C, int dtype,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_conv0_bwd: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(x && w && gamma && beta && dy && sums && dw && dgamma && dbeta && workspace, "debug_conv0_bwd: null pointer");
+  SSAK_REQUIRE(c0_debug_shape(B, T, C), "debug_conv0_bwd: B=%d T=%d C=%d (T >= 10; C / 4 must divide 256)", B, T, C);
+  SSAK_REQUIRE(((uintptr_t)workspace & 7) == 0 && workspace_bytes >= ssak_debug_conv0_bwd_workspace_bytes(B, T, C),
+               "debug_conv0_bwd: workspace too small or not 8-byte aligned");
+  const int T0 = (T - KS0) / ST0 + 1;
+  if (dtype == 0)
+    return k_conv0_gn_gelu_bwd_t<bf16>(x, w, gamma, beta, (const bf16*)dy, sums, (float*)workspace, dw, dgamma, dbeta, B, T, T0, C,
+                                       (hipStream_t)stream);
+  return k_conv0_gn_gelu_bwd_t<float>(x, w, gamma, beta, (const float*)dy, sums, (float*)workspace, dw, dgamma, dbeta, B, T, T0, C,
+                                      (hipStream_t)stream);
+}
+
+extern "C" size_t ssak_debug_conv0_wgrad_workspace_bytes(int B, int C, int ksize) {
+  if (B <= 0 || C <= 0 || ksize <= 0) return 0;
+  return k_conv0_wgrad_scratch_floats(B, C, ksize) * sizeof(float);
+}
+
+extern "C" int ssak_debug_conv0_wgrad(const void* d, const float* x, float* dw, int B, int T, int C, int ksize, int stride, int dtype,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_conv0_wgrad: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(d && x && dw && workspace, "debug_conv0_wgrad: null pointer");
+  SSAK_REQUIRE(B > 0 && B <= 65535 && C > 0 && ksize > 0 && stride > 0 && T >= ksize, "debug_conv0_wgrad: B=%d T=%d C=%d k=%d s=%d", B, T,
+               C, ksize, stride);
+  SSAK_REQUIRE(ksize <= 10 && stride * 64 + ksize <= 64 * 5 + 16 && C <= 512 && (C & 1) == 0,
+               "debug_conv0_wgrad: k=%d s=%d C=%d outside what is built (k <= 10, 64 s + k <= 336, C even and <= 512)", ksize, stride, C);
+  SSAK_REQUIRE(workspace_bytes >= ssak_debug_conv0_wgrad_workspace_bytes(B, C, ksize), "debug_conv0_wgrad: workspace too small");
+  const int T0 = (T - ksize) / stride + 1;
+  if (dtype == 0)
+    return k_conv0_wgrad_t<bf16>((const bf16*)d, x, dw, (float*)workspace, B, T, T0, C, ksize, stride, (hipStream_t)stream);
+  return k_conv0_wgrad_t<float>((const float*)d, x, dw, (float*)workspace, B, T, T0, C, ksize, stride, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_conv0_bias(const float* x, const float* w, const float* bias, void* out, int B, int T, int C, int dtype,
+                                     void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_conv0_bias: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(x && w && out, "debug_conv0_bias: null pointer");
+  SSAK_REQUIRE(c0_debug_shape(B, T, C), "debug_conv0_bias: B=%d T=%d C=%d (T >= 10; C / 4 must divide 256)", B, T, C);
+  const int T0 = (T - KS0) / ST0 + 1;
+  if (dtype == 0) return k_conv0_bias_t<bf16>(x, w, bias, (bf16*)out, B, T, T0, C, KS0, ST0, (hipStream_t)stream);
+  return k_conv0_bias_t<float>(x, w, bias, (float*)out, B, T, T0, C, KS0, ST0, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_col2im(const void* dxcol, void* dx, int B, int Tin, int Tout, int C, int k, int s, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_col2im: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(dxcol && dx, "debug_col2im: null pointer");
+  SSAK_REQUIRE(B > 0 && Tin > 0 && Tout > 0 && C > 0 && k > 0 && s > 0, "debug_col2im: B=%d Tin=%d Tout=%d C=%d k=%d s=%d", B, Tin, Tout,
+               C, k, s);
+  SSAK_REQUIRE((C & 7) == 0, "debug_col2im: C=%d must be a multiple of 8", C);
+  if (dtype == 0) return k_col2im_t<bf16>((const bf16*)dxcol, (bf16*)dx, B, Tin, Tout, C, k, s, (hipStream_t)stream);
+  return k_col2im_t<float>((const float*)dxcol, (float*)dx, B, Tin, Tout, C, k, s, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_sum_slabs(const float* slabs, int nb, long n, float* out, void* stream) {
+  SSAK_REQUIRE(slabs && out, "debug_sum_slabs: null pointer");
+  SSAK_REQUIRE(nb > 0 && n > 0, "debug_sum_slabs: nb=%d n=%ld", nb, n);
+  return k_sum_slabs(slabs, nb, n, out, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_conv_weight_rearrange(const float* w, void* out, int Co, int Ci, int k, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_conv_weight_rearrange: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(w && out, "debug_conv_weight_rearrange: null pointer");
+  SSAK_REQUIRE(Co > 0 && Ci > 0 && k > 0, "debug_conv_weight_rearrange: Co=%d Ci=%d k=%d", Co, Ci, k);
+  if (dtype == 0) return k_conv_weight_rearrange_t<bf16>(w, (bf16*)out, Co, Ci, k, (hipStream_t)stream);
+  return k_conv_weight_rearrange_t<float>(w, (float*)out, Co, Ci, k, (hipStream_t)stream);
+}

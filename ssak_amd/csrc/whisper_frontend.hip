@@ -151,3 +151,48 @@ int k_conv_wgrad_unrearrange(const float* dwr, float* g, int Co, int Ci, int k, 
   SSAK_LAUNCH_CHECK();
   return SSAK_OK;
 }
+
+// ---- debug: one launch function each (tests/test_gpu_frontend.py).  Nothing on the hot path calls these.
+extern "C" int ssak_debug_conv_wgrad_unrearrange(const float* dwr, float* g, int Co, int Ci, int k, void* stream) {
+  SSAK_REQUIRE(dwr && g, "debug_conv_wgrad_unrearrange: null pointer");
+  SSAK_REQUIRE(Co > 0 && Ci > 0 && k > 0, "debug_conv_wgrad_unrearrange: Co=%d Ci=%d k=%d", Co, Ci, k);
+  return k_conv_wgrad_unrearrange(dwr, g, Co, Ci, k, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_col2im_k3s2(const void* dxcol, const void* pre, void* out, int B, int F, int Tin, int RS1, int H, int dtype,
+                                      void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_col2im_k3s2: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(dxcol && pre && out, "debug_col2im_k3s2: null pointer");
+  // F frames of Conv1d(k = 3, s = 2, pad = 1) over Tin rows; pre holds row u of utterance b at row b * RS1 + 1 + u of its B * RS1
+  SSAK_REQUIRE(B > 0 && Tin > 0 && F == (Tin + 1) / 2 && RS1 >= Tin + 1 && H > 0 && (H & 7) == 0,
+               "debug_col2im_k3s2: B=%d F=%d Tin=%d RS1=%d H=%d (F = (Tin + 1) / 2, RS1 > Tin, H %% 8 == 0)", B, F, Tin, RS1, H);
+  if (dtype == 0)
+    return k_col2im_k3s2_t<bf16>((const bf16*)dxcol, (const bf16*)pre, (bf16*)out, B, F, Tin, RS1, H, (hipStream_t)stream);
+  return k_col2im_k3s2_t<float>((const float*)dxcol, (const float*)pre, (float*)out, B, F, Tin, RS1, H, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_mel_to_cl(const float* mel, void* cl, int B, int C, int T, int RS, int lead, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_mel_to_cl: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(mel && cl, "debug_mel_to_cl: null pointer");
+  SSAK_REQUIRE(B > 0 && B <= 65535 && C > 0 && T > 0 && lead >= 0 && RS >= lead + T, "debug_mel_to_cl: B=%d C=%d T=%d RS=%d lead=%d", B, C,
+               T, RS, lead);
+  if (dtype == 0) return k_mel_to_cl_t<bf16>(mel, (bf16*)cl, B, C, T, RS, lead, (hipStream_t)stream);
+  return k_mel_to_cl_t<float>(mel, (float*)cl, B, C, T, RS, lead, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_add_rowvec(const void* x, const void* pos, void* out, int B, int F, int H, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_add_rowvec: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(x && pos && out, "debug_add_rowvec: null pointer");
+  SSAK_REQUIRE(B > 0 && F > 0 && H > 0 && (H & 7) == 0, "debug_add_rowvec: B=%d F=%d H=%d (H %% 8 == 0)", B, F, H);
+  if (dtype == 0) return k_add_rowvec_t<bf16>((const bf16*)x, (const bf16*)pos, (bf16*)out, B, F, H, (hipStream_t)stream);
+  return k_add_rowvec_t<float>((const float*)x, (const float*)pos, (float*)out, B, F, H, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_copy_rows_padded(const void* src, void* dst, int B, int F, int RS, int H, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_copy_rows_padded: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(src && dst, "debug_copy_rows_padded: null pointer");
+  SSAK_REQUIRE(B > 0 && F > 0 && RS >= F && H > 0 && (H & 7) == 0, "debug_copy_rows_padded: B=%d F=%d RS=%d H=%d (RS >= F, H %% 8 == 0)", B,
+               F, RS, H);
+  if (dtype == 0) return k_copy_rows_padded_t<bf16>((const bf16*)src, (bf16*)dst, B, F, RS, H, (hipStream_t)stream);
+  return k_copy_rows_padded_t<float>((const float*)src, (float*)dst, B, F, RS, H, (hipStream_t)stream);
+}

@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 560  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 570  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -186,6 +186,19 @@ def _load():
         "ssak_debug_posconv_direct": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
         "ssak_debug_posconv_wgrad": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
         "ssak_debug_posconv_weight_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+        "ssak_debug_conv0_bwd_workspace_bytes": (sz, [i32, i32, i32]),
+        "ssak_debug_conv0_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+        "ssak_debug_conv0_wgrad_workspace_bytes": (sz, [i32, i32, i32]),
+        "ssak_debug_conv0_wgrad": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+        "ssak_debug_conv0_bias": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        "ssak_debug_col2im": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "ssak_debug_sum_slabs": (i32, [vp, i32, C.c_long, vp, vp]),
+        "ssak_debug_conv_weight_rearrange": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+        "ssak_debug_conv_wgrad_unrearrange": (i32, [vp, vp, i32, i32, i32, vp]),
+        "ssak_debug_col2im_k3s2": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+        "ssak_debug_mel_to_cl": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+        "ssak_debug_add_rowvec": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+        "ssak_debug_copy_rows_padded": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     }
     lib.ssak_version.restype = i32
     got = lib.ssak_version()
@@ -693,3 +706,85 @@ def debug_posconv_weight_bwd(dwf, g, v, norms, dg, dv, G: int):
     """``k_posconv_weight_bwd``: dg [K], dv [H, cg, K] += the weight-norm backward of dwf; norms from ``debug_posconv_prepare``."""
     H, cg, K = v.shape
     check(lib.ssak_debug_posconv_weight_bwd(ptr(dwf), ptr(g), ptr(v), ptr(norms), ptr(dg), ptr(dv), H, G, K, stream()))
+
+
+# ------------------------------------------------------------------ test-only: the trained feature encoder's kernels and the
+# Whisper front end's data movers (ABI 570).  Every wrapper launches into the caller's buffers.
+def debug_conv0_bwd_workspace(B: int, T: int, C_: int, device):
+    """The scratch of ``debug_conv0_bwd``, every byte 0xFF (NaN as fp32 and as fp64)."""
+    nbytes = lib.ssak_debug_conv0_bwd_workspace_bytes(B, T, C_)
+    return torch.full((max(int(nbytes), 16),), 0xFF, dtype=torch.uint8, device=device)
+
+
+def debug_conv0_bwd(x, w, gamma, beta, dy, sums, dw, dgamma, dbeta, *, workspace=None):
+    """``k_conv0_gn_gelu_bwd_t``: x [B, T], w [C, 10], dy [B, T0, C] (bf16 or fp32), sums [B, C, 2] float64 (mean, rstd);
+    dw [C, 10], dgamma [C], dbeta [C] +=."""
+    B, T = x.shape
+    Cc = w.shape[0]
+    ws = workspace if workspace is not None else debug_conv0_bwd_workspace(B, T, Cc, x.device)
+    check(lib.ssak_debug_conv0_bwd(ptr(x), ptr(w), ptr(gamma), ptr(beta), ptr(dy), ptr(sums), ptr(dw), ptr(dgamma), ptr(dbeta), B, T, Cc,
+                                   _row_dtype(dy), ptr(ws), ws.numel(), stream()))
+
+
+def debug_conv0_wgrad(d, x, dw, stride: int, *, workspace=None):
+    """``k_conv0_wgrad_t``: d [B, T0, C], x [B, T]; dw [C, ksize] +=."""
+    B, T = x.shape
+    Cc, ksize = dw.shape
+    nbytes = lib.ssak_debug_conv0_wgrad_workspace_bytes(B, Cc, ksize)
+    ws = workspace if workspace is not None else torch.full((max(int(nbytes), 16),), 0xFF, dtype=torch.uint8, device=x.device)
+    check(lib.ssak_debug_conv0_wgrad(ptr(d), ptr(x), ptr(dw), B, T, Cc, ksize, int(stride), _row_dtype(d), ptr(ws), ws.numel(), stream()))
+
+
+def debug_conv0_bias(x, w, bias, out):
+    """``k_conv0_bias_t``: out [>= B * T0, C] = conv0(x) + bias (bias may be None)."""
+    B, T = x.shape
+    check(lib.ssak_debug_conv0_bias(ptr(x), ptr(w), ptr(bias), ptr(out), B, T, w.shape[0], _row_dtype(out), stream()))
+
+
+def debug_col2im(dxcol, dx, k: int, s: int):
+    """``k_col2im_t``: dxcol [B, Tout, k, C] -> dx [B, Tin, C]."""
+    B, Tout, kk, Cc = dxcol.shape
+    assert kk == k and dx.shape[0] == B and dx.shape[2] == Cc
+    check(lib.ssak_debug_col2im(ptr(dxcol), ptr(dx), B, dx.shape[1], Tout, Cc, k, s, _row_dtype(dx), stream()))
+
+
+def debug_sum_slabs(slabs, out):
+    """``k_sum_slabs``: slabs [nb, n] fp32 -> out [n]."""
+    nb, n = slabs.shape
+    check(lib.ssak_debug_sum_slabs(ptr(slabs), nb, n, ptr(out), stream()))
+
+
+def debug_conv_weight_rearrange(w, out):
+    """``k_conv_weight_rearrange_t``: w [Co, Ci, k] fp32 -> out [Co, k, Ci] (bf16 or fp32)."""
+    Co, Ci, k = w.shape
+    check(lib.ssak_debug_conv_weight_rearrange(ptr(w), ptr(out), Co, Ci, k, _row_dtype(out), stream()))
+
+
+def debug_conv_wgrad_unrearrange(dwr, g):
+    """``k_conv_wgrad_unrearrange``: g [Co, Ci, k] += dwr [Co, k, Ci]."""
+    Co, Ci, k = g.shape
+    check(lib.ssak_debug_conv_wgrad_unrearrange(ptr(dwr), ptr(g), Co, Ci, k, stream()))
+
+
+def debug_col2im_k3s2(dxcol, pre, out, Tin: int):
+    """``k_col2im_k3s2_t``: dxcol [B, F, 3, H], pre [B * RS1, H] (one-row lead) -> out [B, RS1, H]."""
+    B, F, _, H = dxcol.shape
+    check(lib.ssak_debug_col2im_k3s2(ptr(dxcol), ptr(pre), ptr(out), B, F, Tin, out.shape[1], H, _row_dtype(out), stream()))
+
+
+def debug_mel_to_cl(mel, cl, RS: int, lead: int):
+    """``k_mel_to_cl_t``: mel [B, C, T] fp32 -> rows b RS + lead + t of cl [rows, C]."""
+    B, Cc, T = mel.shape
+    check(lib.ssak_debug_mel_to_cl(ptr(mel), ptr(cl), B, Cc, T, RS, lead, _row_dtype(cl), stream()))
+
+
+def debug_add_rowvec(x, pos, out):
+    """``k_add_rowvec_t``: out [B, F, H] = x + pos [F, H]."""
+    B, F, H = x.shape
+    check(lib.ssak_debug_add_rowvec(ptr(x), ptr(pos), ptr(out), B, F, H, _row_dtype(x), stream()))
+
+
+def debug_copy_rows_padded(src, dst):
+    """``k_copy_rows_padded_t``: src [B, F, H] -> dst [B, RS, H], rows >= F zero."""
+    B, F, H = src.shape
+    check(lib.ssak_debug_copy_rows_padded(ptr(src), ptr(dst), B, F, dst.shape[1], H, _row_dtype(src), stream()))
