@@ -487,7 +487,8 @@ int ssak_w2v2_backward(ssak_w2v2* h, const float* dlogits, void* workspace, size
 /* The same model stopped at the encoder's last hidden state -- `self.modules.wav2vec2(wavs)` of the SpeechBrain recipe
  * (ssak/train/speechbrain/wav2vec_train.py:51; HuggingFaceWav2Vec2 returns Wav2Vec2Model(wav)[0]): hidden [B,F,H] bf16 out, no
  * final dropout, no lm_head.  ssak_w2v2_backward_hidden continues from d loss / d hidden [B,F,H] bf16 (the unfrozen case,
- * :95-137); the lm_head gradient stays zero.  A backward must match the kind of forward that preceded it. */
+ * :95-137); the lm_head gradient stays zero.  A backward must match the kind of forward that preceded it.  In the fp32-exact
+ * mode (since ABI 580; refused before) hidden and dhidden are float [B,F,H], the engine's storage type in that mode. */
 int ssak_w2v2_forward_hidden(ssak_w2v2* h, const float* input_values, const int32_t* lens, int B, int T,
                              const uint8_t* spec_mask, const uint8_t* layer_keep /*host*/, uint64_t seed, int training,
                              void* hidden_bf16, int32_t* frame_lens, void* workspace, size_t workspace_bytes, void* stream);
@@ -621,6 +622,51 @@ int ssak_augment_time_stretch(const float* x, const int32_t* lens, const int32_t
 #define SSAK_AUG_FIR_TILE 2048
 int ssak_augment_fir_drop(const float* x, int B, int T, const float* taps, int ntaps, const int32_t* chunks, const int32_t* chunk_counts,
                           const int32_t* chunk_counts_host /*host*/, int max_chunks, float* out, void* stream);
+
+/* ---- utterance classification on the encoder (ABI 580): pooling, head, loss ------------------------------------------------
+ * What ssak/utils/gender.py's Wav2Vec2ForSpeechClassification / HubertForSpeechClassification compute after the encoder
+ * (:51-133, :155-237; reached from predict_gender, :242-301): hidden [B, F, H] -> merged_strategy (mean / sum / max over time)
+ * -> dropout -> Linear(H, H) -> tanh -> dropout -> Linear(H, C) -> softmax or CrossEntropyLoss, and the autograd of that
+ * chain back to d loss / d hidden for ssak_w2v2_backward_hidden.  Host-side composition: ssak_amd/classify.py.  Every sum
+ * runs in a fixed order (no float atomics): results are bit-reproducible.  No timing of these kernels has been measured.
+ *
+ * Pooling.  hidden / dhidden [B, F, H] of `dtype` 0 = bf16 (the engine) or 1 = fp32 (the fp32-exact mode), 16-byte aligned,
+ * H a multiple of 8, B <= 65535.  frame_lens [B] int32 on the device and frame_lens_host, THE SAME VALUES in host memory
+ * (validated before any launch: 1 <= len <= F, so a zero length is SSAK_ERR_INVALID) -- both or neither; NULL pools all F
+ * frames, padding included: the reference's torch.mean(hidden, dim=1).  With lengths only frames < len are pooled and mean
+ * divides by len.  pooled [B, H] fp32; max also writes argmax [B, H] int32, the LOWEST frame that attains the maximum (NULL
+ * for the other modes).  The host copy is what is CHECKED and the device copy is what the kernels READ: a binder keeps one
+ * source for both.  Should they disagree, nothing faults -- the kernels clamp a device length into [0, F] (a row of length 0
+ * pools to 0, or to -inf under max, with argmax 0) and a device label outside [0, C) gives a NaN loss -- but the result is not the checked one.
+ * Backward: dhidden is written whole -- dpooled / len (mean), dpooled (sum) or dpooled at the argmax
+ * frame (max), exact zeros at frames >= len and everywhere else. */
+#define SSAK_POOL_MEAN 0
+#define SSAK_POOL_SUM 1
+#define SSAK_POOL_MAX 2
+int ssak_pool_fwd(const void* hidden, const int32_t* frame_lens, const int32_t* frame_lens_host /*host*/, int B, int F, int H, int mode,
+                  int dtype, float* pooled, int32_t* argmax, void* stream);
+int ssak_pool_bwd(const float* dpooled, const int32_t* argmax, const int32_t* frame_lens, const int32_t* frame_lens_host /*host*/, int B,
+                  int F, int H, int mode, int dtype, void* dhidden, void* stream);
+/* The head, all fp32: z = drop(pooled) W1^T + b1, act = tanh(z) [B, H] (saved for the backward), logits = drop(act) W2^T + b2
+ * [B, C]; W1 [H, H], b1 [H], W2 [C, H], b2 [C] as nn.Linear stores them; H a multiple of 4, matrices and activations 16-byte
+ * aligned.  Both dropouts use probability drop_p under `seed` with the library's counter-based mask on the sites below, (row,
+ * col) = (utterance, feature) of the [B, H] tensor: ssak_debug_dropout_mask(seed, site, drop_p, B, H) reproduces them.
+ * training == 0 or drop_p == 0: no dropout.  Backward (same drop_p / seed / training as the forward): dW1, db1, dW2, db2
+ * OVERWRITTEN, dpooled [B, H]; workspace >= ssak_cls_head_bwd_workspace_bytes, 16-byte aligned. */
+#define SSAK_CLS_SITE_INPUT 4  /* dropout of the pooled vector, in front of `dense` */
+#define SSAK_CLS_SITE_HIDDEN 5 /* dropout of tanh(dense), in front of `out_proj` */
+int ssak_cls_head_fwd(const float* pooled, const float* W1, const float* b1, const float* W2, const float* b2, int B, int H, int C,
+                      float drop_p, uint64_t seed, int training, float* act, float* logits, void* stream);
+size_t ssak_cls_head_bwd_workspace_bytes(int B, int H, int C);
+int ssak_cls_head_bwd(const float* dlogits, const float* pooled, const float* act, const float* W1, const float* W2, int B, int H, int C,
+                      float drop_p, uint64_t seed, int training, float* dW1, float* db1, float* dW2, float* db2, float* dpooled,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* probs [B, C] = softmax(logits).  With labels [B] int32 (device) and labels_host (the same values in host memory, validated
+ * before the launch: a label outside [0, C) is SSAK_ERR_INVALID) -- both or neither -- also loss [1] = the mean over the batch
+ * of -log probs[b, label_b] (CrossEntropyLoss, gender.py:117-119) and dlogits [B, C] = (probs - onehot) / B * grad_scale;
+ * either may be NULL.  Without labels loss and dlogits must be NULL. */
+int ssak_cls_softmax_ce(const float* logits, const int32_t* labels, const int32_t* labels_host /*host*/, int B, int C, float grad_scale,
+                        float* probs, float* loss, float* dlogits, void* stream);
 
 /* ---- TEST-ONLY entries (not part of the product path; kept in the release library so that the parity tests run against the
  * library that ships): dropout bits of one site ------------------------------------------------------------------------

@@ -18,7 +18,7 @@ void ssak_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int ssak_version(void) { return 570; }  // ssak_debug_conv0_* / _col2im* / ... test entries (INTEGRATION.md "ABI 570")
+extern "C" int ssak_version(void) { return 580; }  // ssak_pool_* / ssak_cls_*: utterance classification (INTEGRATION.md "ABI 580")
 extern "C" const char* ssak_last_error(void) { return g_err; }
 
 // ---- optional per-launch timing (bench.py's roofline leg): HIP events around launches, on the launch's own stream ----

@@ -956,7 +956,7 @@ extern "C" int ssak_w2v2_num_frames(const ssak_w2v2* e, int T) {
 // (Wav2Vec2Model()[0], what the SpeechBrain recipe's wav2vec2 module returns) and no head.
 template <typename AT>
 static int forward_impl(ssak_w2v2* e, const float* input_values, const int32_t* lens, int B, int T, const uint8_t* spec_mask,
-                        const uint8_t* layer_keep /*host*/, uint64_t seed, int training, float* logits, bf16* hidden,
+                        const uint8_t* layer_keep /*host*/, uint64_t seed, int training, float* logits, void* hidden /*AT [M, H]*/,
                         int32_t* frame_lens, void* workspace, size_t workspace_bytes, void* stream) {
   SSAK_REQUIRE(e && input_values && (logits || hidden) && workspace, "w2v2_forward: null pointer");
   SSAK_REQUIRE(e->P && e->W, "w2v2_forward: bind + sync_weights first");
@@ -1197,8 +1197,7 @@ static int forward_impl(ssak_w2v2* e, const float* input_values, const int32_t* 
   // ---- a8: final dropout + lm_head -> fp32 logits
   const AT* xl = BF(e->xin[c.num_layers]);
   if (hidden) {
-    SSAK_REQUIRE(!EXACT, "w2v2_forward_hidden: the hidden-state interface is bf16 (not built for the fp32-exact mode)");
-    SSAK_HIP(hipMemcpyAsync(hidden, xl, (size_t)M * H * sizeof(bf16), hipMemcpyDeviceToDevice, st));
+    SSAK_HIP(hipMemcpyAsync(hidden, xl, (size_t)M * H * sizeof(AT), hipMemcpyDeviceToDevice, st));  // (float in the fp32-exact mode)
     e->have_fwd = tr;
     e->fwd_hidden = true;
     return SSAK_OK;
@@ -1231,14 +1230,16 @@ extern "C" int ssak_w2v2_forward_hidden(ssak_w2v2* e, const float* input_values,
                                         int training, void* hidden_bf16, int32_t* frame_lens, void* workspace,
                                         size_t workspace_bytes, void* stream) {
   SSAK_REQUIRE(e && hidden_bf16, "w2v2_forward_hidden: null pointer");
-  SSAK_REQUIRE(!e->cfg.exact, "w2v2_forward_hidden: not built for the fp32-exact mode");
-  return forward_impl<bf16>(e, input_values, lens, B, T, spec_mask, layer_keep, seed, training, nullptr, (bf16*)hidden_bf16, frame_lens,
+  if (e->cfg.exact)  // the hidden state in the mode's storage type: float [B, F, H]
+    return forward_impl<float>(e, input_values, lens, B, T, spec_mask, layer_keep, seed, training, nullptr, hidden_bf16, frame_lens,
+                               workspace, workspace_bytes, stream);
+  return forward_impl<bf16>(e, input_values, lens, B, T, spec_mask, layer_keep, seed, training, nullptr, hidden_bf16, frame_lens,
                       workspace, workspace_bytes, stream);
 }
 
 // dlogits (after ssak_w2v2_forward) or dhidden (after ssak_w2v2_forward_hidden): exactly one is non-null
 template <typename AT>
-static int backward_impl(ssak_w2v2* e, const float* dlogits, const bf16* dhidden, void* workspace, size_t workspace_bytes,
+static int backward_impl(ssak_w2v2* e, const float* dlogits, const void* dhidden /*AT [M, H]*/, void* workspace, size_t workspace_bytes,
                          void* stream) {
   SSAK_REQUIRE(e && (dlogits || dhidden) && workspace, "w2v2_backward: null pointer");
   if (!e->have_fwd || e->fwd_hidden != (dhidden != nullptr)) {
@@ -1314,7 +1315,7 @@ static int backward_impl(ssak_w2v2* e, const float* dlogits, const bf16* dhidden
   AT* gA = BF(p.dA);  // gradient w.r.t. the current layer output = gA (+ gB)
   AT* gB = nullptr;
   if (dhidden)
-    SSAK_HIP(hipMemcpyAsync(gA, dhidden, (size_t)M * H * sizeof(bf16), hipMemcpyDeviceToDevice, st));
+    SSAK_HIP(hipMemcpyAsync(gA, dhidden, (size_t)M * H * sizeof(AT), hipMemcpyDeviceToDevice, st));
   else {
     // dx = (dlogits W) * mask / (1 - p): the final-dropout mask is replayed in this product's epilogue ((row, column) of the [M, H]
     // output = the site's indices; through round 5 a pass of its own over gA, 14 us per step)
@@ -1675,6 +1676,6 @@ extern "C" int ssak_w2v2_backward(ssak_w2v2* e, const float* dlogits, void* work
 extern "C" int ssak_w2v2_backward_hidden(ssak_w2v2* e, const void* dhidden_bf16, void* workspace, size_t workspace_bytes,
                                          void* stream) {
   SSAK_REQUIRE(e && dhidden_bf16, "w2v2_backward_hidden: null pointer");
-  SSAK_REQUIRE(!e->cfg.exact, "w2v2_backward_hidden: not built for the fp32-exact mode");
-  return backward_impl<bf16>(e, nullptr, (const bf16*)dhidden_bf16, workspace, workspace_bytes, stream);
+  if (e->cfg.exact) return backward_impl<float>(e, nullptr, dhidden_bf16, workspace, workspace_bytes, stream);
+  return backward_impl<bf16>(e, nullptr, dhidden_bf16, workspace, workspace_bytes, stream);
 }

@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 570  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 580  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -170,6 +170,12 @@ def _load():
         "ssak_comm_create": (i32, [C.POINTER(vp), i32, i32, vp]),
         "ssak_allreduce": (i32, [vp, vp, C.c_long, C.c_long, i32, vp]),
         "ssak_comm_destroy": (i32, [vp]),
+        "ssak_pool_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "ssak_pool_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+        "ssak_cls_head_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, C.c_uint64, i32, vp, vp, vp]),
+        "ssak_cls_head_bwd_workspace_bytes": (sz, [i32, i32, i32]),
+        "ssak_cls_head_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, C.c_uint64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "ssak_cls_softmax_ce": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]),
         "ssak_debug_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, C.c_long, i32, vp, C.POINTER(f32), vp]),
         "ssak_debug_attention_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, i32, i32, i32, vp, vp]),
         "ssak_debug_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, C.c_uint64, C.c_uint32, f32, C.c_uint32,
@@ -606,6 +612,92 @@ def attention_bwd_bias(qkv, ctx, lse, dctx, B: int, F: int, nh: int, klens=None,
     check(lib.ssak_attention_bwd_bias(ptr(qkv), ptr(ctx), ptr(lse), ptr(klens), ptr(dctx), ptr(delta), ptr(dqkv), ptr(bias_grad), B, F,
                                       nh, H, float(drop_p), seed, stream_id, ptr(ws), nbytes, stream()))
     return dqkv, bias_grad
+
+
+# ------------------------------------------------------------------ utterance classification (ABI 580): pooling, head, loss
+POOL_MODES = {"mean": 0, "sum": 1, "max": 2}  # SSAK_POOL_*
+CLS_SITE_INPUT, CLS_SITE_HIDDEN = 4, 5  # SSAK_CLS_SITE_*: the head's two dropout sites on its [B, H] tensors
+
+
+def _host_i32(values, n: int, what: str):
+    """The host mirror of a small int32 device vector (lengths, labels): the library validates it before any launch."""
+    if torch.is_tensor(values):
+        values = values.detach().cpu().numpy()
+    a = np.ascontiguousarray(values, dtype=np.int32).reshape(-1)
+    if a.shape != (n,):
+        raise ValueError(f"{what}: expected {n} values, got {a.shape[0]}")
+    return a
+
+
+def pool_fwd(hidden: torch.Tensor, frame_lens=None, mode: str = "mean"):
+    """hidden [B,F,H] bf16 (or fp32, the exact mode) -> (pooled [B,H] fp32, argmax [B,H] int32 | None) over the frames
+    ``< frame_lens[b]`` (host values; None = all F frames, padding included).  ``ssak_pool_fwd``."""
+    assert hidden.is_cuda and hidden.dim() == 3 and hidden.is_contiguous()
+    B, F, H = hidden.shape
+    lens_h = None if frame_lens is None else _host_i32(frame_lens, B, "frame_lens")
+    lens_d = None if lens_h is None else torch.from_numpy(lens_h).to(hidden.device)
+    pooled = torch.empty((B, H), dtype=torch.float32, device=hidden.device)
+    argmax = torch.empty((B, H), dtype=torch.int32, device=hidden.device) if mode == "max" else None
+    check(lib.ssak_pool_fwd(ptr(hidden), ptr(lens_d), _hp(lens_h), B, F, H, POOL_MODES[mode], _row_dtype(hidden), ptr(pooled), ptr(argmax),
+                            stream()))
+    return pooled, argmax
+
+
+def pool_bwd(dpooled: torch.Tensor, argmax, frame_lens, F: int, mode: str = "mean", dtype: torch.dtype = torch.bfloat16):
+    """d loss / d pooled [B,H] fp32 -> d loss / d hidden [B,F,H] of ``dtype``, every element written (``ssak_pool_bwd``)."""
+    assert dpooled.is_cuda and dpooled.dtype == torch.float32 and dpooled.dim() == 2 and dpooled.is_contiguous()
+    B, H = dpooled.shape
+    lens_h = None if frame_lens is None else _host_i32(frame_lens, B, "frame_lens")
+    lens_d = None if lens_h is None else torch.from_numpy(lens_h).to(dpooled.device)
+    dhidden = torch.empty((B, int(F), H), dtype=dtype, device=dpooled.device)
+    check(lib.ssak_pool_bwd(ptr(dpooled), ptr(argmax), ptr(lens_d), _hp(lens_h), B, int(F), H, POOL_MODES[mode], _row_dtype(dhidden),
+                            ptr(dhidden), stream()))
+    return dhidden
+
+
+def cls_head_fwd(pooled, W1, b1, W2, b2, drop_p: float = 0.0, seed: int = 0, training: bool = False):
+    """pooled [B,H] fp32 -> (logits [B,C], act [B,H] = tanh(dense(drop(pooled))), saved for the backward).  ``ssak_cls_head_fwd``."""
+    B, H = pooled.shape
+    Cn = W2.shape[0]
+    act = torch.empty((B, H), dtype=torch.float32, device=pooled.device)
+    logits = torch.empty((B, Cn), dtype=torch.float32, device=pooled.device)
+    check(lib.ssak_cls_head_fwd(ptr(pooled), ptr(W1), ptr(b1), ptr(W2), ptr(b2), B, H, Cn, float(drop_p), C.c_uint64(int(seed)), int(bool(training)),
+                                ptr(act), ptr(logits), stream()))
+    return logits, act
+
+
+def cls_head_bwd(dlogits, pooled, act, W1, W2, dW1, db1, dW2, db2, drop_p: float = 0.0, seed: int = 0, training: bool = False):
+    """The head's backward into the caller's gradient tensors (overwritten) -> d loss / d pooled [B,H].  ``ssak_cls_head_bwd``."""
+    B, H = pooled.shape
+    Cn = W2.shape[0]
+    dpooled = torch.empty_like(pooled)
+    ws = _ws(lib.ssak_cls_head_bwd_workspace_bytes(B, H, Cn), pooled.device)
+    check(lib.ssak_cls_head_bwd(ptr(dlogits), ptr(pooled), ptr(act), ptr(W1), ptr(W2), B, H, Cn, float(drop_p), C.c_uint64(int(seed)),
+                                int(bool(training)), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2), ptr(dpooled), ptr(ws), ws.numel(), stream()))
+    return dpooled
+
+
+def cls_softmax_ce(logits: torch.Tensor, labels=None, grad_scale: float = 1.0, want_grad: bool = True):
+    """logits [B,C] fp32 -> (probs [B,C], loss [1] | None, dlogits [B,C] | None); ``labels`` are host values (or a tensor, read
+    back once), validated by the library before the launch.  ``ssak_cls_softmax_ce``."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
+    B, Cn = logits.shape
+    probs = torch.empty_like(logits)
+    lab_h = None if labels is None else _host_i32(labels, B, "labels")
+    lab_d = None if lab_h is None else torch.from_numpy(lab_h).to(logits.device)
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device) if lab_h is not None else None
+    dlogits = torch.empty_like(logits) if lab_h is not None and want_grad else None
+    check(lib.ssak_cls_softmax_ce(ptr(logits), ptr(lab_d), _hp(lab_h), B, Cn, float(grad_scale), ptr(probs), ptr(loss), ptr(dlogits), stream()))
+    return probs, loss, dlogits
+
+
+# ------------------------------------------------------------------ test-only: the dropout bits of one site
+def debug_dropout_mask(seed: int, site: int, p: float, rows: int, cols: int, device):
+    """(keep [rows, cols] uint8, scale) of one dropout site (``ssak_debug_dropout_mask``)."""
+    keep = torch.empty((rows, cols), dtype=torch.uint8, device=device)
+    scale = C.c_float()
+    check(lib.ssak_debug_dropout_mask(C.c_uint64(int(seed)), int(site), float(p), rows, cols, ptr(keep), C.byref(scale), stream()))
+    return keep, scale.value
 
 
 # ------------------------------------------------------------------ test-only: the row kernels of norm_act.hip (ABI 540)

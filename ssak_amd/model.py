@@ -344,13 +344,13 @@ class Wav2Vec2ForCTC:
 
     def forward_hidden(self, input_values: torch.Tensor, attention_mask=None, mask_time_indices=None, layer_keep=None,
                        lengths=None, keep_graph: Optional[bool] = None):
-        """The encoder's last hidden state [B, F, H] bf16 -- ``Wav2Vec2Model(wav)[0]``, what the SpeechBrain recipe's
-        ``modules.wav2vec2`` wraps (ssak/train/speechbrain/wav2vec_train.py:51).  ``keep_graph`` (default: training mode)
-        keeps the activations for :meth:`backward_hidden`."""
+        """The encoder's last hidden state [B, F, H] bf16 (float in the fp32-exact mode) -- ``Wav2Vec2Model(wav)[0]``, what the
+        SpeechBrain recipe's ``modules.wav2vec2`` wraps (ssak/train/speechbrain/wav2vec_train.py:51).  ``keep_graph`` (default:
+        training mode) keeps the activations for :meth:`backward_hidden`."""
         training = self.training
         x, B, T, F, lens_dev, ws, mask_dev, keep_arr, flens = self._prelude(input_values, attention_mask, mask_time_indices,
                                                                             layer_keep, lengths, training)
-        hidden = torch.empty((B, F, self.config.hidden_size), dtype=torch.bfloat16, device=self.device)
+        hidden = torch.empty((B, F, self.config.hidden_size), dtype=torch.float32 if self.exact else torch.bfloat16, device=self.device)
         with torch.cuda.device(self.device):
             hip.check(hip.lib.ssak_w2v2_forward_hidden(self._h, hip.ptr(x), hip.ptr(lens_dev), B, T, hip.ptr(mask_dev), keep_arr,
                                                        C.c_uint64(self._used_seed), int(training), hip.ptr(hidden),
@@ -359,10 +359,11 @@ class Wav2Vec2ForCTC:
         return hidden, flens
 
     def backward_hidden(self, dhidden: torch.Tensor):
-        """d loss / d params from d loss / d hidden [B, F, H] bf16 (the unfrozen wav2vec2 of the SpeechBrain recipe)."""
+        """d loss / d params from d loss / d hidden [B, F, H] bf16, float in the fp32-exact mode (the unfrozen wav2vec2 of the
+        SpeechBrain recipe)."""
         if self._last is None or not isinstance(self._last[0], str):
             raise RuntimeError("backward_hidden() needs a training-mode forward_hidden()")
-        assert dhidden.dtype == torch.bfloat16 and dhidden.is_contiguous()
+        assert dhidden.dtype == (torch.float32 if self.exact else torch.bfloat16) and dhidden.is_contiguous()
         with torch.cuda.device(self.device):
             hip.check(hip.lib.ssak_w2v2_backward_hidden(self._h, hip.ptr(dhidden), hip.ptr(self._ws), self._ws.numel(),
                                                         hip.stream()))
