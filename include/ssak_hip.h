@@ -403,6 +403,13 @@ typedef struct {
    * comparable with the fp32 reference at 1e-4 instead of bf16's 1e-2.  wav2vec2 topologies with the frozen feature
    * encoder; a few per cent of the bf16 mode's speed.  Workspace sizes double. */
   int exact;
+  /* ABI 590: MMS language adapters (transformers Wav2Vec2AttnAdapterLayer, config.adapter_attn_dim).  0 = none: parameter
+   * table, buffer plan and launch sequence are those of ABI 580.  > 0 (16, MMS's value, is the one supported): every encoder
+   * layer ends with h = h + W2 relu(W1 LN(h) + b1) + b2 after its feed-forward residual, LN a plain LayerNorm with eps 1e-5
+   * whatever layer_norm_eps says; the parameter table gains wav2vec2.encoder.layers.N.adapter_layer.{norm,linear_1,linear_2}.
+   * {weight,bias} per layer after lm_head.bias.  Needs arch 0 and do_stable_layer_norm 1 (HF's post-LN layer has no
+   * adapter).  Inference only: a training-mode forward and the backward are SSAK_ERR_INVALID on such a handle. */
+  int adapter_attn_dim;
 } ssak_w2v2_config;
 typedef struct ssak_w2v2 ssak_w2v2;
 
@@ -713,6 +720,17 @@ int ssak_debug_softmax_fwd(const void* S, void* P, void* Pd, const int32_t* klen
 int ssak_debug_softmax_bwd(const void* dPd, const void* P, void* dS, int rows, int cols, int ld, uint64_t seed, uint32_t site, float p,
                            int dtype, void* stream);
 int ssak_debug_gelu(const float* x, long n, float* y, float* dydx, int dtype, void* stream);
+
+/* ---- TEST-ONLY entry (ABI 590): the closing row kernel of an adapter layer (attn_adapter.hip), one launch -----------------
+ * r2 = res + y (y may be NULL), r2' = r2 + W2 relu(W1 LN_a(r2) + b1) + b2 -> r_out (rounded to the storage type; may alias
+ * res or y), out = LN_next(r2') of the stored values, mean / rstd [M] fp32 its statistics (both or neither).  LN_a = (ln_g,
+ * ln_b, eps_adapter), LN_next = (next_g, next_b, eps_next), biased variance.  dtype 0: y, res, r_out, out, w1 [A,H], w2 [H,A]
+ * bf16 (the products are bf16 MFMAs with fp32 accumulation, LN_a(r2) and relu(..) rounded to bf16 on the way in); dtype 1:
+ * all of them fp32, fp32 FMA throughout.  A must be 16, H a multiple of 8 and <= 1536; anything else is SSAK_ERR_INVALID. */
+int ssak_test_attn_adapter_fwd(const void* y, const void* res, const float* ln_g, const float* ln_b, const void* w1, const float* b1,
+                               const void* w2, const float* b2, const float* next_g, const float* next_b, void* r_out, void* out,
+                               float* mean, float* rstd, int M, int H, int A, float eps_adapter, float eps_next, int dtype,
+                               void* stream);
 
 /* ---- TEST-ONLY entries (ABI 550): the grouped positional convolution (posconv.hip, conv_frontend.hip), one stage each ---
  * Each calls the k_posconv_* launch functions the engine calls, with the engine's arguments (rows_per_group = K / 2 +

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import dataclasses
 import json
-from typing import Tuple
+from typing import Optional, Tuple
 
 
 @dataclasses.dataclass
@@ -38,6 +38,7 @@ class Wav2Vec2Config:
     pad_token_id: int = 0
     ctc_loss_reduction: str = "mean"
     ctc_zero_infinity: bool = True
+    adapter_attn_dim: Optional[int] = None  # MMS language adapters (Wav2Vec2AttnAdapterLayer); None = none (0 in the engine)
 
     def deterministic(self) -> "Wav2Vec2Config":
         return dataclasses.replace(self, attention_dropout=0.0, hidden_dropout=0.0, activation_dropout=0.0,
@@ -45,6 +46,9 @@ class Wav2Vec2Config:
 
     @classmethod
     def from_hf_dict(cls, d: dict) -> "Wav2Vec2Config":
+        if d.get("add_adapter"):
+            raise ValueError("add_adapter = true (the convolutional Wav2Vec2Adapter on top of the encoder) is not implemented; "
+                             "the language adapters of MMS are adapter_attn_dim")
         names = {f.name for f in dataclasses.fields(cls)}
         kw = {k: (tuple(v) if isinstance(v, list) else v) for k, v in d.items() if k in names}
         return cls(**kw)

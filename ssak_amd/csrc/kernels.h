@@ -145,6 +145,15 @@ int k_posconv_weight_bwd(const float* dw, const float* g, const float* v, const 
 template <typename T>
 int k_posconv_pack_t(const T* h, T* pg, int B, int F, int H, int G, int K, hipStream_t st);
 
+// attn_adapter.hip: the closing row kernel of a stable-LN layer with an MMS language adapter, one launch:
+// r2 = res + y (y may be null), r2' = r2 + W2 relu(W1 LN_a(r2) + b1) + b2 -> r_out (may alias res / y), LN_next(r2') -> out
+// (+ its mean / rstd, both or neither).  w1 [A,H], w2 [H,A] in the storage type T; A = 16 only.
+bool k_attn_adapter_supported(int H, int A);
+template <typename T>
+int k_attn_adapter_fwd_t(const T* y, const T* res, const float* ln_g, const float* ln_b, const T* w1, const float* b1, const T* w2,
+                         const float* b2, const float* next_g, const float* next_b, T* r_out, T* out, float* mean, float* rstd, int M,
+                         int H, int A, float eps_adapter, float eps_next, hipStream_t st);
+
 // attention.hip (fused, head_dim 64)
 bool k_attention_supported(int H, int nh);
 int k_attention_fwd(const bf16* qkv, bf16* ctx, float* lse, const int32_t* klens, int B, int F, int nh, int H,

@@ -36,6 +36,7 @@ struct PInfo {
 
 struct LayerP {
   long wqkv, bqkv, wo, bo, ln1w, ln1b, w1, b1, w2, b2, ln2w, ln2b;
+  long ad_nw = 0, ad_nb = 0, ad_w1 = 0, ad_b1 = 0, ad_w2 = 0, ad_b2 = 0;  // MMS language adapter (cfg.adapter_attn_dim > 0)
 };
 
 inline long align_up(long x, long a) { return (x + a - 1) / a * a; }
@@ -263,6 +264,20 @@ void build_param_table(ssak_w2v2* e) {
     add_param(e, cur, p + "final_layer_norm.bias", {H}, 0, &L.ln2b);
   }
   add_param(e, cur, "lm_head.bias", {V}, 0, &e->p_lm_b);
+  if (c.adapter_attn_dim > 0) {
+    // MMS language adapters (Wav2Vec2AttnAdapterLayer): behind everything else, so that a table without them is unchanged
+    const long A = c.adapter_attn_dim;
+    for (int l = 0; l < c.num_layers; ++l) {
+      const std::string p = "wav2vec2.encoder.layers." + std::to_string(l) + ".adapter_layer.";
+      LayerP& L = e->lp[l];
+      add_param(e, cur, p + "norm.weight", {H}, 0, &L.ad_nw);
+      add_param(e, cur, p + "norm.bias", {H}, 0, &L.ad_nb);
+      add_param(e, cur, p + "linear_1.weight", {A, H}, 0, &L.ad_w1);
+      add_param(e, cur, p + "linear_1.bias", {A}, 0, &L.ad_b1);
+      add_param(e, cur, p + "linear_2.weight", {H, A}, 0, &L.ad_w2);
+      add_param(e, cur, p + "linear_2.bias", {H}, 0, &L.ad_b2);
+    }
+  }
   e->n_train = cur;
   // region 1: feature encoder (frozen by default, wav2vec_train.py:326-327)
   long cin = 1;
@@ -280,6 +295,13 @@ void build_param_table(ssak_w2v2* e) {
 }
 
 int check_config(const ssak_w2v2_config& c) {
+  if (c.adapter_attn_dim != 0) {
+    SSAK_REQUIRE(c.arch == 0 && c.do_stable_layer_norm == 1,
+                 "w2v2: adapter_attn_dim needs arch 0 and do_stable_layer_norm = 1 (the post-LN encoder layer of transformers has no adapter)");
+    SSAK_REQUIRE(k_attn_adapter_supported(c.hidden_size, c.adapter_attn_dim),
+                 "w2v2: adapter_attn_dim %d with hidden_size %d unsupported (supported values: adapter_attn_dim 16, hidden_size a multiple of 8 up to 1536)",
+                 c.adapter_attn_dim, c.hidden_size);
+  }
   if (c.arch == 1) {
     SSAK_REQUIRE(c.num_mel_bins > 0 && c.num_mel_bins % 8 == 0 && c.max_source_positions > 0, "whisper: num_mel_bins must be a multiple of 8");
     SSAK_REQUIRE(c.hidden_size % c.num_heads == 0 && (c.hidden_size / c.num_heads) % 8 == 0, "whisper: head_dim must be a multiple of 8");
@@ -962,6 +984,8 @@ static int forward_impl(ssak_w2v2* e, const float* input_values, const int32_t* 
   SSAK_REQUIRE(e->P && e->W, "w2v2_forward: bind + sync_weights first");
   SSAK_REQUIRE(B > 0 && T > 0, "w2v2_forward: bad shape B=%d T=%d", B, T);
   SSAK_REQUIRE(((uintptr_t)workspace & 255) == 0, "w2v2_forward: workspace must be 256-byte aligned");
+  SSAK_REQUIRE(!(training && e->cfg.adapter_attn_dim > 0),
+               "w2v2_forward: a model with language adapters (adapter_attn_dim > 0) runs inference only: training is not implemented");
   constexpr bool EXACT = sizeof(AT) == 4;  // fp32-exact verification mode (ssak_w2v2_config.exact)
   EngineCall engine_call(e);
   Plan& p = e->plan;
@@ -1189,8 +1213,15 @@ static int forward_impl(ssak_w2v2* e, const float* input_values, const int32_t* 
                           M, H, c.layer_norm_eps, DS(c.hidden_dropout, ds_hid2(l)), none, st));
     } else {
       // r2 = r1 + drop(ffn);  x[l+1] = (next layer's LN1 | encoder LN)(r2)
-      TRY(k_layernorm_fwd_t<AT>(BF(p.tmpH), BF(lb.r1), nxt_w, nxt_b, BF(lb.r2), BF(p.x[l + 1]), stl + 2 * M, stl + 3 * M, M, H,
-                          c.layer_norm_eps, DS(c.hidden_dropout, ds_hid2(l)), none, st));
+      if (c.adapter_attn_dim > 0)
+        // ... with the language adapter between them: r2' = r2 + adapter(r2), x[l+1] = LN(r2') (attn_adapter.hip; inference
+        // only, so no dropout site; the adapter's LayerNorm is a plain nn.LayerNorm: eps 1e-5, not layer_norm_eps)
+        TRY(k_attn_adapter_fwd_t<AT>(BF(p.tmpH), BF(lb.r1), P + L.ad_nw, P + L.ad_nb, W + L.ad_w1, P + L.ad_b1, W + L.ad_w2, P + L.ad_b2,
+                                     nxt_w, nxt_b, BF(lb.r2), BF(p.x[l + 1]), stl + 2 * M, stl + 3 * M, M, H, c.adapter_attn_dim, 1e-5f,
+                                     c.layer_norm_eps, st));
+      else
+        TRY(k_layernorm_fwd_t<AT>(BF(p.tmpH), BF(lb.r1), nxt_w, nxt_b, BF(lb.r2), BF(p.x[l + 1]), stl + 2 * M, stl + 3 * M, M, H,
+                            c.layer_norm_eps, DS(c.hidden_dropout, ds_hid2(l)), none, st));
       e->hres[l + 1] = lb.r2;
     }
   }
@@ -1242,6 +1273,8 @@ template <typename AT>
 static int backward_impl(ssak_w2v2* e, const float* dlogits, const void* dhidden /*AT [M, H]*/, void* workspace, size_t workspace_bytes,
                          void* stream) {
   SSAK_REQUIRE(e && (dlogits || dhidden) && workspace, "w2v2_backward: null pointer");
+  SSAK_REQUIRE(e->cfg.adapter_attn_dim == 0,
+               "w2v2_backward: a model with language adapters (adapter_attn_dim > 0) runs inference only: training is not implemented");
   if (!e->have_fwd || e->fwd_hidden != (dhidden != nullptr)) {
     ssak_set_error("w2v2_backward: no matching training-mode forward to differentiate");
     return SSAK_ERR_STATE;

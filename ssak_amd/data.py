@@ -229,27 +229,73 @@ def remove_special_words(text: str, glue_apostrophe: Optional[bool] = True) -> s
     return _SPACES.sub(" ", text).strip()
 
 
+def _tokens_in_id_order(table: Dict[str, int]) -> List[str]:
+    return [t for t, _ in sorted(table.items(), key=lambda kv: kv[1])]
+
+
 class CharTokenizer:
     """Character CTC tokenizer with the conventions of ``Wav2Vec2CTCTokenizer``: ``|`` is the word delimiter,
     pad token = CTC blank, decoding merges repeats, drops pad, maps the delimiter to a space."""
 
-    def __init__(self, vocab: Sequence[str], pad_token="<pad>", unk_token="<unk>", word_delimiter_token="|"):
-        self.vocab = list(vocab)
-        self.index = {t: i for i, t in enumerate(self.vocab)}
-        self.pad_token_id = self.index[pad_token]
-        self.unk_token_id = self.index.get(unk_token, self.pad_token_id)
+    def __init__(self, vocab, pad_token="<pad>", unk_token="<unk>", word_delimiter_token="|", target_lang: Optional[str] = None):
+        """``vocab``: the tokens in id order, or -- the nested vocabulary of an MMS checkpoint -- ``{language: {token: id}}``
+        with ``target_lang`` naming the language in use (default: the first one)."""
+        self._pad_token, self._unk_token = pad_token, unk_token
         self.delim = word_delimiter_token
+        self.nested: Optional[Dict[str, Dict[str, int]]] = None
+        self.target_lang: Optional[str] = None
+        if isinstance(vocab, dict):
+            self.nested = {lang: dict(table) for lang, table in vocab.items()}
+            self.set_target_lang(target_lang if target_lang is not None else next(iter(self.nested)))
+        else:
+            self._use(list(vocab))
+
+    def _use(self, vocab: List[str]):
+        self.vocab = vocab
+        self.index = {t: i for i, t in enumerate(self.vocab)}
+        self.pad_token_id = self.index[self._pad_token]
+        self.unk_token_id = self.index.get(self._unk_token, self.pad_token_id)
         self.special = {t for t in self.vocab if t.startswith("<") and t.endswith(">")}
+
+    @property
+    def languages(self) -> List[str]:
+        """The languages of a nested (MMS) vocabulary; empty for a flat one."""
+        return list(self.nested) if self.nested is not None else []
+
+    def set_target_lang(self, target_lang: str):
+        """Switch the vocabulary to ``target_lang`` (``Wav2Vec2CTCTokenizer.set_target_lang``, same errors)."""
+        if self.nested is None:
+            raise ValueError(f"{self.index} is not a multi-lingual, nested tokenizer. Cannot set target language.")
+        if target_lang not in self.nested:
+            raise ValueError(f"{target_lang} does not exist. Choose one of {', '.join(self.nested)}.")
+        self.target_lang = target_lang
+        self._use(_tokens_in_id_order(self.nested[target_lang]))
 
     @classmethod
     def from_vocab_json(cls, path: str, **kw) -> "CharTokenizer":
+        """``vocab.json``: ``{token: id}``, or ``{language: {token: id}}`` (MMS) with the language in use read from
+        ``target_lang`` of a sibling ``tokenizer_config.json`` when there is one."""
         with open(path) as f:
             d = json.load(f)
-        return cls([t for t, _ in sorted(d.items(), key=lambda kv: kv[1])], **kw)
+        if d and all(isinstance(v, dict) for v in d.values()):
+            cfg = os.path.join(os.path.dirname(path), "tokenizer_config.json")
+            if "target_lang" not in kw and os.path.isfile(cfg):
+                with open(cfg) as f:
+                    kw["target_lang"] = json.load(f).get("target_lang")
+            return cls(d, **kw)
+        return cls(_tokens_in_id_order(d), **kw)
 
     def save(self, folder: str):
         with open(os.path.join(folder, "vocab.json"), "w") as f:
-            json.dump(self.index, f, ensure_ascii=False)
+            json.dump(self.index if self.nested is None else self.nested, f, ensure_ascii=False)
+        if self.nested is not None:  # the language in use travels in tokenizer_config.json, as HF writes it
+            cfg_path, cfg = os.path.join(folder, "tokenizer_config.json"), {}
+            if os.path.isfile(cfg_path):
+                with open(cfg_path) as f:
+                    cfg = json.load(f)
+            cfg["target_lang"] = self.target_lang
+            with open(cfg_path, "w") as f:
+                json.dump(cfg, f, ensure_ascii=False, indent=1)
 
     def __len__(self):
         return len(self.vocab)

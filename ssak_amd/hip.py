@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 580  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 590  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -36,7 +36,7 @@ class W2V2Config(C.Structure):
                 ("layer_norm_eps", C.c_float), ("attention_dropout", C.c_float), ("hidden_dropout", C.c_float),
                 ("activation_dropout", C.c_float), ("feat_proj_dropout", C.c_float), ("final_dropout", C.c_float),
                 ("freeze_feature_encoder", C.c_int), ("arch", C.c_int), ("num_mel_bins", C.c_int),
-                ("max_source_positions", C.c_int), ("exact", C.c_int)]
+                ("max_source_positions", C.c_int), ("exact", C.c_int), ("adapter_attn_dim", C.c_int)]
 
 
 class ProfEntry(C.Structure):
@@ -186,6 +186,7 @@ def _load():
         "ssak_debug_softmax_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, C.c_uint64, C.c_uint32, f32, i32, vp]),
         "ssak_debug_softmax_bwd": (i32, [vp, vp, vp, i32, i32, i32, C.c_uint64, C.c_uint32, f32, i32, vp]),
         "ssak_debug_gelu": (i32, [vp, C.c_long, vp, vp, i32, vp]),
+        "ssak_test_attn_adapter_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, vp]),
         "ssak_debug_posconv_prepare": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
         "ssak_debug_posconv_pack": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
         "ssak_debug_posconv_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
@@ -749,6 +750,23 @@ def debug_gelu(x: torch.Tensor, dtype: torch.dtype):
     y, d = torch.empty_like(x), torch.empty_like(x)
     check(lib.ssak_debug_gelu(ptr(x), x.numel(), ptr(y), ptr(d), 0 if dtype == torch.bfloat16 else 1, stream()))
     return y, d
+
+
+# ------------------------------------------------------------------ test-only: the adapter layer's closing row kernel (ABI 590)
+def test_attn_adapter_fwd(y, res, ln_g, ln_b, w1, b1, w2, b2, next_g, next_b, r_out, out, mean=None, rstd=None, *, eps_adapter=1e-5,
+                          eps_next=1e-5):
+    """One ``k_attn_adapter_fwd_t`` launch into the caller's buffers (``ssak_test_attn_adapter_fwd``): y (or None), res, r_out, out
+    [M, H] and w1 [A, H], w2 [H, A] all bf16 or all fp32; the LayerNorm affines and the biases fp32."""
+    M, H = res.shape
+    A = w1.shape[0]
+    dt = _row_dtype(res)
+    assert all(t is None or t.dtype == res.dtype for t in (y, w1, w2, r_out, out)), "activations and W1 / W2 share one storage type"
+    check(lib.ssak_test_attn_adapter_fwd(ptr(y), ptr(res), ptr(ln_g), ptr(ln_b), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(next_g),
+                                         ptr(next_b), ptr(r_out), ptr(out), ptr(mean), ptr(rstd), M, H, A, float(eps_adapter),
+                                         float(eps_next), dt, stream()))
+
+
+test_attn_adapter_fwd.__test__ = False  # (a binding, not a test: keep collectors that import this module away from it)
 
 
 # ------------------------------------------------------------------ test-only: the grouped positional convolution (ABI 550)

@@ -29,12 +29,37 @@ def transformers_load_model(source, device=None):
     return model.eval(), tok
 
 
+def resolve_language(tokenizer, language: Optional[str]) -> Optional[str]:
+    """``--language`` against a nested (MMS) vocabulary, as transformers_infer.py:51-61: the exact name, else the one language
+    it is a prefix of, else ``ValueError`` with the candidates.  Other tokenizers leave ``language`` as it is."""
+    languages = list(getattr(tokenizer, "languages", None) or [])
+    if language is None or not languages or language in languages:
+        return language
+    candidates = [l for l in languages if l.startswith(language)]
+    if len(candidates) == 0:
+        raise ValueError(f"Language {language} not in {languages}")
+    if len(candidates) > 1:
+        raise ValueError(f"Language {language} not in {languages}.\nCould it be one of {candidates}?")
+    return candidates[0]
+
+
 def transformers_compute_logits(model, processor, batch: List[np.ndarray], device=None, language=None,
                                 sample_rate: int = 16000, max_duration: int = MAX_SAMPLES) -> torch.Tensor:
     """list of float32 waveforms -> CPU fp32 logits [B, F, V] (transformers_infer.py:190-269): normalise + pad
     (a1, on the device), forward; inputs longer than ``max_duration`` samples are split on the sample axis and the
     logits concatenated on the frame axis (:259-265).  Group-norm ("base") models run without attention mask, as HF
     prescribes for them; layer-norm models get the lengths."""
+    if language is not None:
+        # MMS: the language's vocabulary and adapter (transformers_infer.py:205-214); a tokenizer that is not multi-lingual
+        # makes `language` a no-op there, any other error is the caller's
+        try:
+            processor.set_target_lang(language)
+        except ValueError as err:
+            if "is not a multi-lingual" not in str(err):
+                raise
+            language = None
+        if language is not None:
+            model.load_adapter(language)
     lens = np.array([len(a) for a in batch], dtype=np.int32)
     T = int(lens.max())
     x = np.zeros((len(batch), T), dtype=np.float32)
@@ -73,16 +98,19 @@ def transformers_infer(source, audios, batch_size: int = 1, device=None, languag
     """Generator of transcripts (or (id, transcript)) -- greedy CTC path of transformers_infer.py:73-95, or with ``arpa_path``
     the LM beam search of :97-133 (ssak_amd.lm; ``alpha`` / ``beta`` weigh the LM).  The LM is loaded once per call."""
     model, tok = transformers_load_model(source, device)
+    language = resolve_language(tok, language)
     lm = None
     if arpa_path is not None:
         from . import lm as lm_mod
+        if language is not None and getattr(tok, "nested", None) is not None:
+            tok.set_target_lang(language)  # the LM's label table is built over the selected language's vocabulary (:116-117)
         lm = lm_mod.load_arpa(arpa_path, tok, model.device)
     for batch in to_audio_batches(audios, batch_size=batch_size, sort_by_len=sort_by_len, output_ids=output_ids):
         ids = None
         if output_ids:
             ids = [b[1] for b in batch]
             batch = [b[0] for b in batch]
-        logits = transformers_compute_logits(model, tok, batch).to(model.device).contiguous()
+        logits = transformers_compute_logits(model, tok, batch, language=language).to(model.device).contiguous()
         # argmax + collapse on the device (a12); only the short id strings cross PCIe
         lens = torch.tensor([model.num_frames(len(a)) for a in batch], dtype=torch.int32)
         with torch.cuda.device(model.device):

@@ -105,6 +105,7 @@ class Wav2Vec2ForCTC:
         c.activation_dropout, c.feat_proj_dropout = config.activation_dropout, config.feat_proj_dropout
         c.final_dropout = config.final_dropout
         c.freeze_feature_encoder = int(freeze_feature_encoder)
+        c.adapter_attn_dim = int(getattr(config, "adapter_attn_dim", None) or 0)  # MMS language adapters (None <-> 0)
         return c
 
     @classmethod
@@ -216,6 +217,56 @@ class Wav2Vec2ForCTC:
                     raise RuntimeError(f"size mismatch for {n}: {tuple(t.shape)} vs {shape}")
                 self.params[off:off + numel].copy_(t.reshape(-1).to(self.device), non_blocking=True)
         self.sync_weights(full=True)
+        return self
+
+    # ------------------------------------------------------------------ MMS language adapters
+    target_lang: Optional[str] = None  # the language whose adapter load_adapter() loaded last (None: what the checkpoint held)
+    name_or_path: Optional[str] = None  # the folder load_pretrained() read: where load_adapter() looks for adapter.<lang>.*
+
+    def load_adapter(self, target_lang: str, folder: Optional[str] = None):
+        """``Wav2Vec2ForCTC.load_adapter`` of transformers (modeling_wav2vec2.py:1067-1250): read ``adapter.<lang>.safetensors``
+        (else ``adapter.<lang>.bin``), require its keys to be exactly the adapter parameters + ``lm_head.{weight,bias}``
+        (``ValueError`` naming unexpected / missing keys), resize the head when the language's vocabulary has another size
+        (a new engine for the new ``vocab_size``; every other parameter is carried over on the device), overwrite those
+        tensors.  Loading the language that is loaded already does nothing."""
+        from .checkpoint import adapter_param_names, read_adapter_state
+        cfg = self.config
+        if not cfg.adapter_attn_dim:
+            raise ValueError(f"Cannot load_adapter for {target_lang} if `config.adapter_attn_dim` is not defined.")
+        if target_lang == self.target_lang:
+            return self
+        folder = folder or self.name_or_path
+        if folder is None:
+            raise ValueError("load_adapter: the model was not loaded from a folder; pass folder=")
+        sd = read_adapter_state(folder, target_lang, adapter_param_names(cfg.num_hidden_layers))
+        V = int(sd["lm_head.weight"].shape[0])
+        if V != cfg.vocab_size:
+            import dataclasses
+            Vp = (V + 7) // 8 * 8
+            self.config = dataclasses.replace(cfg, vocab_size=V)
+            if Vp != self._c.vocab_size:
+                # the head's shape is part of the engine's parameter table: a new engine, the other parameters copied across
+                self.wait_params()
+                old_params, old_layout, old_h = self._params, self.layout, self._h
+                c = self._c
+                c.vocab_size = Vp
+                torch.cuda.synchronize(self.device)
+                self._h = None
+                hip.lib.ssak_w2v2_destroy(old_h)
+                self._finish_init(c, self._seed)
+                for n, (off, numel, shape) in self.layout.items():
+                    if n not in self._HEAD:
+                        o_off, o_numel, o_shape = old_layout[n]
+                        assert o_shape == shape, n
+                        self._params[off:off + numel].copy_(old_params[o_off:o_off + o_numel])
+        for n, t in sd.items():
+            off, numel, shape = self.layout[n]
+            t = self._pad_vocab(n, torch.as_tensor(t).to(torch.float32))
+            if tuple(t.shape) != shape:
+                raise RuntimeError(f"size mismatch for {n}: {tuple(t.shape)} vs {shape}")
+            self._params[off:off + numel].copy_(t.reshape(-1).to(self.device))
+        self.sync_weights(full=True)
+        self.target_lang = target_lang
         return self
 
     def sync_weights(self, full: bool = True):

@@ -187,6 +187,7 @@ def evaluate(model, tok, waves, labels, batch_size, rank: int = 0, world: int = 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    refuse_adapter_training(args.base_model)
     if args.data_augment:
         from .augment import parse_rir_arg
         parse_rir_arg(args.data_augment_rir)  # (the reference's RuntimeErrors before anything else happens, wav2vec_train.py:259-266)
@@ -430,6 +431,17 @@ def sorted_checkpoints(out_dir: str):
 def last_checkpoint(out_dir: str):
     cks = sorted_checkpoints(out_dir)
     return cks[-1] if cks else None
+
+
+def refuse_adapter_training(folder: str):
+    """An MMS checkpoint (``adapter_attn_dim`` in its config.json) runs inference only: the engine has no backward for the
+    language adapters, so say so before anything is loaded or built."""
+    path = os.path.join(folder, "config.json")
+    if os.path.isfile(path):
+        with open(path) as f:
+            if json.load(f).get("adapter_attn_dim"):
+                raise NotImplementedError(f"{folder}: a model with language adapters (adapter_attn_dim > 0) runs inference only: "
+                                          "training is not implemented")
 
 
 def tok_pad(folder: str) -> int:
