@@ -675,6 +675,50 @@ int ssak_cls_head_bwd(const float* dlogits, const float* pooled, const float* ac
 int ssak_cls_softmax_ce(const float* logits, const int32_t* labels, const int32_t* labels_host /*host*/, int B, int C, float grad_scale,
                         float* probs, float* loss, float* dlogits, void* stream);
 
+/* ---- the Whisper text decoder (ABI 600): embedding, attention, per-row log-softmax statistics ------------------------------
+ * The decoder of transformers' WhisperForConditionalGeneration as a teacher-forced pass (ssak/infer/whisper_infer.py and
+ * ssak/train/transformers/whisper_train.py:498-507 run it): these three entries plus ssak_gemm_bf16 (projections, feed-forward,
+ * the vocabulary projection against the tied embedding) and ssak_layernorm_fwd.  Host-side composition:
+ * ssak_amd/whisper_seq2seq.py.  bf16 storage, fp32 accumulation; every sum in a fixed order, no float atomics; no backward, so
+ * nothing is saved.  No per-kernel timing has been measured (whole calls: tools/bench_whisper_decoder.py).
+ *
+ * ssak_dec_embed.  out [B * L, D] bf16, out[b, i, :] = bf16(fp32(embed_tokens[ids[b, i], :]) + fp32(embed_positions[pos_offset +
+ * i, :])); embed_tokens [V, D] and embed_positions [max_positions, D] bf16, D a multiple of 8, all 16-byte aligned.  ids [B * L]
+ * int32 on the device and ids_host, THE SAME VALUES in host memory: the host copy is what is checked (an id outside [0, V), or
+ * pos_offset + L > max_positions, is SSAK_ERR_INVALID and nothing is launched), the device copy is what the kernel reads (and
+ * clamps into the table, should the two disagree).
+ *
+ * ssak_dec_attention_fwd.  ctx [B * Lq, nh * 64] bf16 = softmax(q k^T * 64^-1/2 + mask) v per (utterance, head), the scaling
+ * applied to q (transformers' WhisperAttention).  q [B * Lq, ldq]; k and v are SEPARATE pointers with row strides ldk / ldv and
+ * Lk rows per utterance (utterance b's key j is row b * Lk + j), head h in columns [64 h, 64 h + 64) of each: self-attention
+ * points q, k, v into one packed [B * L, 3 D] buffer (ld = 3 D, Lk = Lq), cross-attention points k, v into the encoder-side
+ * [B * S, 2 D] buffer.  Strides are in elements, multiples of 8 and >= nh * 64; pointers 16-byte aligned.  Visibility: key j is
+ * visible to query i iff j < klens[b] and, when causal != 0, j <= q_offset + i (q_offset: the position of the first query
+ * among the keys -- 0 for a whole sequence, the cache length for an incremental step).  klens [B] int32 (device) and klens_host
+ * (host, the same values) come together or are both NULL (= Lk); the host copy is validated, 1 <= klens[b] <= Lk, so a fully
+ * masked row cannot occur (causal always shows key 0).  head_dim must be 64, the head dimension of every Whisper size: any
+ * other value is SSAK_ERR_INVALID.  P is rounded to bf16 for the second product; the row sum is that of the unrounded P.
+ *
+ * ssak_token_logprobs.  Per row r of logits [R, ldv] (dtype 1 = fp32, 0 = bf16; V valid columns, ldv >= V; columns >= V are
+ * never read): lse[r] = log sum_c exp(logits[r, c]); logprob[r] = logits[r, targets[r]] - lse[r], 0 where targets[r] < 0 (HF's
+ * -100); argmax[r] = the LOWEST column that attains the maximum.  With allowed [n_allowed] column ids (device + host copy) the
+ * softmax runs over those columns only (lse, logprob and argmax with it; ties to the earliest list entry) and probs [R, n_allowed]
+ * receives it: whisper.decoding.detect_language's mask.  targets (device) / targets_host (host) come together; a target >= V
+ * or an allowed id outside [0, V) is SSAK_ERR_INVALID.  lse, logprob, argmax, probs may each be NULL. */
+int ssak_dec_embed(const void* embed_tokens, const void* embed_positions, const int32_t* ids, const int32_t* ids_host /*host*/, int B, int L,
+                   int D, int V, int max_positions, int pos_offset, void* out, void* stream);
+int ssak_dec_attention_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, int Lk, const int32_t* klens,
+                           const int32_t* klens_host /*host*/, int B, int Lq, int nh, int head_dim, int causal, int q_offset, void* ctx,
+                           void* stream);
+int ssak_token_logprobs(const void* logits, int dtype, int R, int V, long ldv, const int32_t* targets, const int32_t* targets_host /*host*/,
+                        const int32_t* allowed, const int32_t* allowed_host /*host*/, int n_allowed, float* lse, float* logprob,
+                        int32_t* argmax, float* probs, void* stream);
+/* r = res + y (either may be NULL) -> r_out (may be NULL), out = LayerNorm(r) * gamma + beta (may be NULL) on [M, C] rows of
+ * dtype 0 = bf16 / 1 = fp32: the row kernel of the encoder layers without dropout sites or saved statistics.  C a multiple of
+ * 8, <= 1536. */
+int ssak_layernorm_fwd(const void* y, const void* res, const float* gamma, const float* beta, void* r_out, void* out, int M, int C,
+                       float eps, int dtype, void* stream);
+
 /* ---- TEST-ONLY entries (not part of the product path; kept in the release library so that the parity tests run against the
  * library that ships): dropout bits of one site ------------------------------------------------------------------------
  * The engine stores no dropout mask: each site recomputes keep(seed, site, element) in its forward and backward kernels

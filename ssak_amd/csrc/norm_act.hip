@@ -1130,6 +1130,24 @@ extern "C" int ssak_debug_layernorm_fwd(const void* y, const void* res, const fl
                                   pre, post, st, mid, post_gelu != 0);
 }
 
+// The residual + LayerNorm row kernel as a product entry (ABI 600): what the Whisper decoder's Python sequencing runs between its
+// GEMMs (ssak_amd/whisper_seq2seq.py) -- no dropout sites, no saved statistics.
+extern "C" int ssak_layernorm_fwd(const void* y, const void* res, const float* gamma, const float* beta, void* r_out, void* out, int M, int C,
+                                  float eps, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "layernorm_fwd: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(M > 0 && C > 0 && (C & 7) == 0 && C <= 1536, "layernorm_fwd: M=%d C=%d (C a multiple of 8, <= 1536)", M, C);
+  SSAK_REQUIRE(y || res, "layernorm_fwd: neither y nor res");
+  SSAK_REQUIRE(out || r_out, "layernorm_fwd: neither out nor r_out");
+  SSAK_REQUIRE(!out || (gamma && beta), "layernorm_fwd: out needs gamma and beta");
+  const DropSpec none;
+  const hipStream_t st = (hipStream_t)stream;
+  if (dtype == 0)
+    return k_layernorm_fwd_t<bf16>((const bf16*)y, (const bf16*)res, gamma, beta, (bf16*)r_out, (bf16*)out, nullptr, nullptr, M, C, eps, none,
+                                   none, st);
+  return k_layernorm_fwd_t<float>((const float*)y, (const float*)res, gamma, beta, (float*)r_out, (float*)out, nullptr, nullptr, M, C, eps, none,
+                                  none, st);
+}
+
 extern "C" size_t ssak_debug_layernorm_bwd_workspace_bytes(int C) { return C > 0 ? (size_t)LN_BWD_BLOCKS * 3 * C * sizeof(float) : 0; }
 
 extern "C" int ssak_debug_layernorm_bwd(const void* g1, const void* g2, const void* r, const float* mean, const float* rstd,

@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 590  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 600  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -176,6 +176,10 @@ def _load():
         "ssak_cls_head_bwd_workspace_bytes": (sz, [i32, i32, i32]),
         "ssak_cls_head_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, C.c_uint64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
         "ssak_cls_softmax_ce": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]),
+        "ssak_dec_embed": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+        "ssak_dec_attention_fwd": (i32, [vp, C.c_long, vp, C.c_long, vp, C.c_long, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+        "ssak_token_logprobs": (i32, [vp, i32, i32, i32, C.c_long, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "ssak_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]),
         "ssak_debug_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, C.c_long, i32, vp, C.POINTER(f32), vp]),
         "ssak_debug_attention_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, i32, i32, i32, vp, vp]),
         "ssak_debug_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, C.c_uint64, C.c_uint32, f32, C.c_uint32,
@@ -690,6 +694,67 @@ def cls_softmax_ce(logits: torch.Tensor, labels=None, grad_scale: float = 1.0, w
     dlogits = torch.empty_like(logits) if lab_h is not None and want_grad else None
     check(lib.ssak_cls_softmax_ce(ptr(logits), ptr(lab_d), _hp(lab_h), B, Cn, float(grad_scale), ptr(probs), ptr(loss), ptr(dlogits), stream()))
     return probs, loss, dlogits
+
+
+# ------------------------------------------------------------------ the Whisper text decoder (ABI 600)
+DEC_HEAD_DIM = 64  # the head dimension of every Whisper size, the one ssak_dec_attention_fwd is built for
+
+
+def dec_embed(embed_tokens: torch.Tensor, embed_positions: torch.Tensor, ids, pos_offset: int = 0, out=None):
+    """ids [B, L] (host values, or a tensor read back once) -> [B * L, D] bf16 = embed_tokens[ids] + embed_positions[pos_offset + i]
+    (``ssak_dec_embed``); a bad id or an overrun of the position table is a ``ValueError`` and launches nothing."""
+    assert embed_tokens.is_cuda and embed_tokens.dtype == torch.bfloat16 and embed_tokens.is_contiguous()
+    assert embed_positions.dtype == torch.bfloat16 and embed_positions.is_contiguous()
+    ids_np = ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)
+    B, L = ids_np.shape
+    V, D = embed_tokens.shape
+    ids_h = np.ascontiguousarray(ids_np, dtype=np.int32).reshape(-1)
+    ids_d = torch.from_numpy(ids_h).to(embed_tokens.device)
+    out = torch.empty((B * L, D), dtype=torch.bfloat16, device=embed_tokens.device) if out is None else out
+    check(lib.ssak_dec_embed(ptr(embed_tokens), ptr(embed_positions), ptr(ids_d), _hp(ids_h), B, L, D, V, embed_positions.shape[0],
+                             int(pos_offset), ptr(out), stream()))
+    return out
+
+
+def dec_attention_fwd(q, k, v, B: int, Lq: int, Lk: int, nh: int, *, klens=None, causal: bool = False, q_offset: int = 0,
+                      head_dim: int = DEC_HEAD_DIM, ctx=None):
+    """``ssak_dec_attention_fwd``: q [B * Lq, ldq], k / v [B * Lk, ldk / ldv] bf16 -- 2-D tensors or column slices of one (their row
+    stride is passed on) -> ctx [B * Lq, nh * 64] bf16.  ``klens``: host values [B] (None: all Lk keys)."""
+    for t in (q, k, v):
+        assert t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1
+    kl_h = None if klens is None else _host_i32(klens, B, "klens")
+    kl_d = None if kl_h is None else torch.from_numpy(kl_h).to(q.device)
+    ctx = torch.empty((B * Lq, nh * head_dim), dtype=torch.bfloat16, device=q.device) if ctx is None else ctx
+    check(lib.ssak_dec_attention_fwd(ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), int(Lk), ptr(kl_d), _hp(kl_h), B, int(Lq),
+                                     int(nh), int(head_dim), int(bool(causal)), int(q_offset), ptr(ctx), stream()))
+    return ctx
+
+
+def token_logprobs(logits: torch.Tensor, V: int, targets=None, allowed=None):
+    """``ssak_token_logprobs`` on logits [R, ldv] (fp32 or bf16, the first V columns valid) -> (lse [R], logprob [R] | None, argmax
+    [R] int32, probs [R, n_allowed] | None).  ``targets`` [R] and ``allowed`` [n] are host values; a negative target is not scored."""
+    assert logits.is_cuda and logits.dim() == 2 and logits.stride(1) == 1
+    R, dev = logits.shape[0], logits.device
+    tg_h = None if targets is None else _host_i32(targets, R, "targets")
+    tg_d = None if tg_h is None else torch.from_numpy(tg_h).to(dev)
+    al_h = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.int32).reshape(-1)
+    al_d = None if al_h is None else torch.from_numpy(al_h).to(dev)
+    n_al = 0 if al_h is None else al_h.shape[0]
+    lse = torch.empty(R, dtype=torch.float32, device=dev)
+    logprob = torch.empty(R, dtype=torch.float32, device=dev) if tg_h is not None else None
+    argmax = torch.empty(R, dtype=torch.int32, device=dev)
+    probs = torch.empty((R, n_al), dtype=torch.float32, device=dev) if n_al else None
+    check(lib.ssak_token_logprobs(ptr(logits), _row_dtype(logits), R, int(V), logits.stride(0), ptr(tg_d), _hp(tg_h), ptr(al_d), _hp(al_h), n_al,
+                                  ptr(lse), ptr(logprob), ptr(argmax), ptr(probs), stream()))
+    return lse, logprob, argmax, probs
+
+
+def layernorm_fwd(y, res, gamma, beta, r_out=None, out=None, eps: float = 1e-5):
+    """``ssak_layernorm_fwd``: r = res + y (either may be None) -> ``r_out``; ``out`` = LayerNorm(r) gamma + beta; [M, C] bf16 or fp32."""
+    x = y if y is not None else res
+    M, Cc = x.shape
+    check(lib.ssak_layernorm_fwd(ptr(y), ptr(res), ptr(gamma), ptr(beta), ptr(r_out), ptr(out), M, Cc, float(eps), _row_dtype(x), stream()))
+    return out if out is not None else r_out
 
 
 # ------------------------------------------------------------------ test-only: the dropout bits of one site

@@ -40,6 +40,10 @@ class WhisperCTCConfig:
     feat_extract_norm: str = "group"  # no attention mask
 
     @property
+    def hidden_size(self):  # (what forward_hidden sizes its output by)
+        return self.d_model
+
+    @property
     def num_hidden_layers(self):
         return self.encoder_layers
 
