@@ -713,6 +713,47 @@ int ssak_dec_attention_fwd(const void* q, long ldq, const void* k, long ldk, con
 int ssak_token_logprobs(const void* logits, int dtype, int R, int V, long ldv, const int32_t* targets, const int32_t* targets_host /*host*/,
                         const int32_t* allowed, const int32_t* allowed_host /*host*/, int n_allowed, float* lse, float* logprob,
                         int32_t* argmax, float* probs, void* stream);
+
+/* ---- Whisper generation (ABI 610): single-query attention against a cache, token selection -------------------------------
+ * The two kernels the greedy generation loop of ssak_amd/whisper_seq2seq.py (`generate`; ssak/infer/whisper_infer.py runs
+ * model.transcribe with temperature 0 and no beam) adds to the ABI 600 entries.  NO PER-CALL HOST COPIES: neither entry takes a
+ * host mirror of a device array and neither reads anything back, so the loop stays on the device between tokens.  fp32
+ * accumulation in a fixed order, no float atomics: two runs on the same inputs give the same bits.
+ *
+ * ssak_dec_attention_step.  ctx [B, nh * 64] bf16 = softmax(q k^T * 64^-1/2 + mask) v for ONE query per (utterance, head), the
+ * scaling applied to q.  q [B, ldq]; k and v are separate pointers, each with a row stride and a per-utterance stride (elements):
+ * utterance b's key j is at k + b * k_batch_stride + j * ldk, head h in columns [64 h, 64 h + 64), so a cache whose capacity
+ * exceeds the keys in use and the [B * S, 2 D] cross buffer are both read in place.  Key j is visible iff j < n_keys (by value:
+ * the cache length of a lock-step batch) and j < klens[b]; klens [B] int32 is optional and DEVICE-ONLY: the caller that uploads
+ * it validates it once (1 <= klens[b]), the kernel clamps it into [1, n_keys].  Rows that are not visible are never read.
+ * The key range is cut into n_split pieces of ceil(n_keys / n_split) keys, one workgroup each; n_split = 0 lets the library choose
+ * (so that the grid covers the chip at least twice where every piece keeps 128 keys; at most 16 pieces), a positive value (<= 64)
+ * forces it.  With more than one piece each writes (max, sum, O[64]) in fp32 to `workspace` (16-byte aligned, at least
+ * ssak_dec_attention_step_workspace_bytes(B, nh, n_split) bytes; may be NULL where one piece results) and a second kernel
+ * combines them in piece order; a piece with no visible key (klens[b] ends before it starts) contributes nothing.
+ * Roundings: products and sums in fp32; P is KEPT IN FP32 into the second product and the row sum is the sum of the same
+ * unrounded P; ctx is rounded to bf16 once.  head_dim != 64, n_keys < 1, a stride that is not a multiple of 8 or is < nh * 64,
+ * a missing or short workspace: SSAK_ERR_INVALID, nothing launched.
+ *
+ * ssak_dec_greedy_step.  Per row b of logits [B, ldv] fp32 (V valid columns; columns >= V are never read): the columns whose
+ * byte in suppress [V] (uint8, device) is non-zero and, when first != 0, those of begin_suppress [V] count as -inf (either
+ * mask may be NULL: transformers' SuppressTokensLogitsProcessor / SuppressTokensAtBeginLogitsProcessor, whisper's
+ * SuppressTokens / SuppressBlank); token = the LOWEST column that attains the maximum of the processed row, logprob = its
+ * log-softmax under the PROCESSED row (whisper/decoding.py: filters first, log_softmax after).  finished [B] (uint8, device) is
+ * read and written: a row that was finished emits pad_id with log-prob 0 and stays finished; a row that emits eos_id becomes
+ * finished.  n_unfinished [1] (int32, device) receives the number of rows still running after the step (zeroed by the entry,
+ * integer atomics).  tokens[b * ldt + t] (int32) and logprobs[b * ldt + t] receive the two results; h_next [B, D] bf16 (may be
+ * NULL) = bf16(fp32(embed_tokens[token]) + fp32(embed_positions[next_pos])), the next step's input row, in the same launch.
+ * eos_id or pad_id outside [0, V), t outside [0, ldt), next_pos >= max_positions (with h_next): SSAK_ERR_INVALID, nothing
+ * launched.  A row whose columns are ALL suppressed is the caller's error; it emits pad_id with log-prob 0. */
+size_t ssak_dec_attention_step_workspace_bytes(int B, int nh, int n_split);
+int ssak_dec_attention_step(const void* q, long ldq, const void* k, long ldk, long k_batch_stride, const void* v, long ldv,
+                            long v_batch_stride, int n_keys, const int32_t* klens, int B, int nh, int head_dim, int n_split, void* workspace,
+                            size_t workspace_bytes, void* ctx, void* stream);
+int ssak_dec_greedy_step(const float* logits, long ldv, int B, int V, const uint8_t* suppress, const uint8_t* begin_suppress, int first,
+                         const void* embed_tokens, const void* embed_positions, int D, int max_positions, int next_pos, int eos_id, int pad_id,
+                         uint8_t* finished, int32_t* n_unfinished, int32_t* tokens, float* logprobs, long ldt, int t, void* h_next,
+                         void* stream);
 /* r = res + y (either may be NULL) -> r_out (may be NULL), out = LayerNorm(r) * gamma + beta (may be NULL) on [M, C] rows of
  * dtype 0 = bf16 / 1 = fp32: the row kernel of the encoder layers without dropout sites or saved statistics.  C a multiple of
  * 8, <= 1536. */

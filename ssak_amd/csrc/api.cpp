@@ -18,7 +18,7 @@ void ssak_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int ssak_version(void) { return 600; }  // the Whisper decoder's kernels: ssak_dec_*, ssak_token_logprobs (INTEGRATION.md "ABI 600")
+extern "C" int ssak_version(void) { return 610; }  // Whisper generation: ssak_dec_attention_step, ssak_dec_greedy_step (INTEGRATION.md "ABI 610")
 extern "C" const char* ssak_last_error(void) { return g_err; }
 
 // ---- optional per-launch timing (bench.py's roofline leg): HIP events around launches, on the launch's own stream ----

@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 600  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 610  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -179,6 +179,9 @@ def _load():
         "ssak_dec_embed": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         "ssak_dec_attention_fwd": (i32, [vp, C.c_long, vp, C.c_long, vp, C.c_long, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         "ssak_token_logprobs": (i32, [vp, i32, i32, i32, C.c_long, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "ssak_dec_attention_step_workspace_bytes": (sz, [i32, i32, i32]),
+        "ssak_dec_attention_step": (i32, [vp, C.c_long, vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, i32, vp, i32, i32, i32, i32, vp, sz, vp, vp]),
+        "ssak_dec_greedy_step": (i32, [vp, C.c_long, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_long, i32, vp, vp]),
         "ssak_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]),
         "ssak_debug_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, C.c_long, i32, vp, C.POINTER(f32), vp]),
         "ssak_debug_attention_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, i32, i32, i32, vp, vp]),
@@ -747,6 +750,54 @@ def token_logprobs(logits: torch.Tensor, V: int, targets=None, allowed=None):
     check(lib.ssak_token_logprobs(ptr(logits), _row_dtype(logits), R, int(V), logits.stride(0), ptr(tg_d), _hp(tg_h), ptr(al_d), _hp(al_h), n_al,
                                   ptr(lse), ptr(logprob), ptr(argmax), ptr(probs), stream()))
     return lse, logprob, argmax, probs
+
+
+# ------------------------------------------------------------------ Whisper generation (ABI 610): no host copies, nothing read back
+def dec_attention_step_workspace(B: int, nh: int, n_split: int = 0, device="cuda:0"):
+    """The fp32 workspace of :func:`dec_attention_step` for ``n_split`` pieces (0: enough for any split the library chooses)."""
+    return torch.empty(max(lib.ssak_dec_attention_step_workspace_bytes(int(B), int(nh), int(n_split)) // 4, 4), dtype=torch.float32, device=device)
+
+
+def dec_attention_step(q, k, v, n_keys: int, nh: int, *, klens=None, n_split: int = 0, workspace=None, head_dim: int = DEC_HEAD_DIM, ctx=None):
+    """``ssak_dec_attention_step``: q [B, ldq]; k / v [B, capacity, ld] bf16 views (row and per-utterance strides are passed on: a
+    cache with spare capacity, column slices of a packed k|v buffer) -> ctx [B, nh * 64] bf16 over the keys ``< n_keys`` and
+    ``< klens[b]``.  ``klens``: an int32 DEVICE tensor [B] the caller has validated (>= 1), or None.  ``n_split``: 0 = the library
+    chooses.  ``workspace``: from :func:`dec_attention_step_workspace` (allocated per call when None)."""
+    assert q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 2 and q.stride(1) == 1
+    for t in (k, v):
+        assert t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 3 and t.stride(2) == 1 and t.shape[0] == q.shape[0]
+    assert klens is None or (klens.is_cuda and klens.dtype == torch.int32 and klens.is_contiguous() and klens.numel() == q.shape[0])
+    B = q.shape[0]
+    if workspace is None:
+        workspace = dec_attention_step_workspace(B, nh, n_split, q.device)
+    ctx = torch.empty((B, nh * head_dim), dtype=torch.bfloat16, device=q.device) if ctx is None else ctx
+    check(lib.ssak_dec_attention_step(ptr(q), q.stride(0), ptr(k), k.stride(1), k.stride(0), ptr(v), v.stride(1), v.stride(0), int(n_keys),
+                                      ptr(klens), B, int(nh), int(head_dim), int(n_split), ptr(workspace), workspace.numel() * 4, ptr(ctx),
+                                      stream()))
+    return ctx
+
+
+def dec_greedy_step(logits, V: int, *, finished, n_unfinished, tokens, logprobs, t: int, eos_id: int, pad_id: int, suppress=None,
+                    begin_suppress=None, first: bool = False, embed_tokens=None, embed_positions=None, next_pos: int = 0, h_next=None):
+    """``ssak_dec_greedy_step`` on logits [B, ldv] fp32: writes ``tokens[:, t]`` (int32 [B, ldt]), ``logprobs[:, t]`` (fp32, same
+    shape), ``finished`` (uint8 [B], read and written), ``n_unfinished`` (int32 [1]) and, when ``h_next`` [B, D] bf16 is given,
+    the next step's input row ``embed_tokens[token] + embed_positions[next_pos]``.  ``suppress`` / ``begin_suppress``: uint8 [V]
+    device masks.  Everything stays on the device."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    B = logits.shape[0]
+    assert tokens.dtype == torch.int32 and logprobs.dtype == torch.float32 and tokens.shape == logprobs.shape and tokens.shape[0] == B
+    assert tokens.is_contiguous() and logprobs.is_contiguous()
+    assert finished.dtype == torch.uint8 and finished.numel() == B and n_unfinished.dtype == torch.int32
+    for m in (suppress, begin_suppress):
+        assert m is None or (m.is_cuda and m.dtype == torch.uint8 and m.numel() == V and m.is_contiguous())
+    D = max_pos = 0
+    if h_next is not None:
+        assert embed_tokens.dtype == torch.bfloat16 and embed_tokens.is_contiguous() and embed_positions.is_contiguous()
+        D, max_pos = embed_tokens.shape[1], embed_positions.shape[0]
+        assert h_next.dtype == torch.bfloat16 and h_next.is_contiguous() and tuple(h_next.shape) == (B, D)
+    check(lib.ssak_dec_greedy_step(ptr(logits), logits.stride(0), B, int(V), ptr(suppress), ptr(begin_suppress), int(bool(first)),
+                                   ptr(embed_tokens), ptr(embed_positions), D, max_pos, int(next_pos), int(eos_id), int(pad_id), ptr(finished),
+                                   ptr(n_unfinished), ptr(tokens), ptr(logprobs), tokens.shape[1], int(t), ptr(h_next), stream()))
 
 
 def layernorm_fwd(y, res, gamma, beta, r_out=None, out=None, eps: float = 1e-5):

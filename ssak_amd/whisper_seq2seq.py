@@ -18,9 +18,18 @@ the residual + LayerNorm between them.  Weights: fp32 masters with a bf16 shadow
 all ``B * L`` rows are never materialised at once: the vocabulary projection and the log-softmax run over chunks of
 ``ROW_CHUNK`` rows, so the workspace is ``ROW_CHUNK * V * 4`` bytes whatever the batch.
 
+Greedy generation (:meth:`WhisperSeq2Seq.generate`, what ssak/infer/whisper_infer.py asks of ``model.transcribe``: temperature 0, no
+beam, ``condition_on_previous_text = False``): every layer's cross k|v projection of the encoder output is computed once per
+call, the prompt is one teacher-forced pass whose self-attention k|v land in a cache, and each further token is one row per
+utterance through the layers -- ``ssak_dec_attention_step`` on the cache and on the cross buffer, ``ssak_dec_greedy_step`` for the
+logits processors, the arg-max, the log-probability, the finished flags and the next input row.  The loop stays on the device:
+the host reads one pinned word every ``poll_every`` steps and the tokens once at the end.
+
 Token ids are the contract (no tokenizer is needed, and none is shipped); :meth:`WhisperSeq2Seq.score_text` is a convenience
-that imports ``transformers.WhisperTokenizer`` lazily.  Not built: KV cache, generation, timestamps, fallback temperatures, beam
-search, training / LoRA, an fp32-exact mode of the decoder.  Timing: tools/bench_whisper_decoder.py (DESIGN.md "Whisper decoder").
+that imports ``transformers.WhisperTokenizer`` lazily.  Not built: timestamps, fallback temperatures, beam search,
+``no_speech_prob``, long-form seeking, ``condition_on_previous_text``, a skinny-M GEMM for the token step, hipGraph capture of the
+step, training / LoRA, an fp32-exact mode of the decoder.  Timing: tools/bench_whisper_decoder.py, tools/bench_whisper_generate.py
+(DESIGN.md "Whisper decoder", "Whisper generation").
 """
 from __future__ import annotations
 
@@ -60,6 +69,13 @@ class WhisperSeq2SeqConfig:
     tie_word_embeddings: bool = True
     activation_function: str = "gelu"
     lang_to_id: Optional[Dict[str, int]] = None  # language code ("fr") -> token id
+    # what generate() reads (generation_config.json; eos / pad also from config.json)
+    eos_token_id: Optional[int] = None
+    pad_token_id: Optional[int] = None
+    suppress_tokens: Optional[List[int]] = None
+    begin_suppress_tokens: Optional[List[int]] = None
+    task_to_id: Optional[Dict[str, int]] = None
+    no_timestamps_token_id: Optional[int] = None
 
     def __post_init__(self):
         for what, heads in (("encoder", self.encoder_attention_heads), ("decoder", self.decoder_attention_heads)):
@@ -92,6 +108,55 @@ class ScoreResult:
     batch_loss: float
     n_scored: np.ndarray
     logprobs: np.ndarray
+
+
+@dataclasses.dataclass
+class GenerateResult:
+    """``tokens``: per utterance the generated ids without the prompt, ending at its ``eos`` if it reached one; ``lens`` [B] their
+    counts; ``token_array`` [B, n] int32, the same ids padded with ``pad`` (n = the longest); ``logprobs`` [B, n] float64, each
+    token's log-softmax under the processed logits, 0 past ``lens``; ``sum_logprob`` [B]; ``avg_logprob`` = sum / (len + 1) as
+    :class:`ScoreResult` has it; ``steps``: the token steps the loop ran before it stopped."""
+    tokens: List[List[int]]
+    lens: np.ndarray
+    token_array: np.ndarray
+    logprobs: np.ndarray
+    sum_logprob: np.ndarray
+    avg_logprob: np.ndarray
+    steps: int
+
+
+# The shortest self-attention cache on which the token step runs ssak_dec_attention_step; below it, ssak_dec_attention_fwd at
+# Lq = 1.  tools/bench_whisper_generate.py times the two side by side (DESIGN.md "Whisper generation"): the step kernel wins
+# beyond the run-to-run range on the cross buffer and on a 448-key cache, at B = 1 and B = 32; on a 64-key cache both are at the
+# launch floor (about 4 us) and their ranges overlap, so a cache of up to 64 keys keeps the older entry.
+STEP_SELF_MIN_KEYS = 65
+
+
+@dataclasses.dataclass
+class _GenState:
+    """What the stepping primitives of :meth:`WhisperSeq2Seq.generate` share.  ``step_cross`` / ``step_self_min_keys``: which
+    attention entry the token step runs -- ssak_dec_attention_step on the cross buffer / on a cache of at least that many keys
+    (None: never), ssak_dec_attention_fwd at Lq = 1 otherwise."""
+    B: int
+    S: int
+    D: int
+    cap: int                              # rows of the self-attention cache
+    enc: torch.Tensor                     # [B, S, D] bf16
+    enc_lens: Optional[torch.Tensor]      # int32 [B] on the device, validated once
+    enc_lens_host: Optional[np.ndarray]   # the same values for the older attention entry (prefill, fallback)
+    cross_kv: torch.Tensor                # [layers, B * S, 2 D]
+    self_kv: torch.Tensor                 # [layers, B, cap, 2 D]
+    ws: torch.Tensor                      # the attention step's split workspace
+    h: torch.Tensor                       # the step's activation rows, [B, D] (f: [B, ffn])
+    h2: torch.Tensor
+    x: torch.Tensor
+    q: torch.Tensor
+    ctx: torch.Tensor
+    y: torch.Tensor
+    f: torch.Tensor
+    step_cross: bool = True
+    step_self_min_keys: Optional[int] = STEP_SELF_MIN_KEYS
+    t: int = 0                            # cache rows in use = the next position
 
 
 def _decoder_layout(cfg: WhisperSeq2SeqConfig):
@@ -180,7 +245,9 @@ class WhisperSeq2Seq:
     def from_pretrained(cls, folder: str, device: str = "cuda:0") -> "WhisperSeq2Seq":
         """An HF ``WhisperForConditionalGeneration`` folder: ``config.json``, ``model.safetensors`` / ``pytorch_model.bin``,
         ``generation_config.json`` for ``lang_to_id`` and ``decoder_start_token_id`` (else the ``<|xx|>`` entries of
-        ``added_tokens.json`` / ``vocab.json``).  Unsupported configurations are refused by name."""
+        ``added_tokens.json`` / ``vocab.json``) and for what :meth:`generate` needs: ``eos_token_id``, ``pad_token_id``,
+        ``suppress_tokens``, ``begin_suppress_tokens``, ``task_to_id``, ``no_timestamps_token_id``.  Unsupported configurations are
+        refused by name."""
         from .checkpoint import load_state_dict_file
         if not os.path.isdir(folder):
             raise FileNotFoundError(f"{folder}: not a model folder (nothing is downloaded: pass a local folder in the HuggingFace layout)")
@@ -193,8 +260,12 @@ class WhisperSeq2Seq:
             with open(gen) as f:
                 g = json.load(f)
             lang_to_id = g.get("lang_to_id")
-            if g.get("decoder_start_token_id") is not None:
-                extra["decoder_start_token_id"] = g["decoder_start_token_id"]
+            for key in ("decoder_start_token_id", "eos_token_id", "pad_token_id", "suppress_tokens", "begin_suppress_tokens", "task_to_id",
+                        "no_timestamps_token_id"):
+                if g.get(key) is not None:
+                    extra[key] = g[key]
+            if isinstance(extra.get("eos_token_id"), list):  # (newer generation configs list several: the first is <|endoftext|>)
+                extra["eos_token_id"] = extra["eos_token_id"][0]
         if not lang_to_id:
             lang_to_id = {}
             for name in ("added_tokens.json", "vocab.json"):
@@ -252,8 +323,11 @@ class WhisperSeq2Seq:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=self.device)
         return hip.gemm(x, w, out, M, N, K, lda=K, ldb=K, ldc=N, bias=bias, epilogue=epilogue)
 
-    def _decoder_hidden(self, enc: torch.Tensor, tokens: np.ndarray, enc_lens=None, pos_offset: int = 0) -> torch.Tensor:
-        """The decoder stack on ``tokens`` [B, L] (teacher forcing) -> the final LayerNorm's output [B * L, D] bf16."""
+    def _decoder_hidden(self, enc: torch.Tensor, tokens: np.ndarray, enc_lens=None, pos_offset: int = 0, cross_kv=None,
+                        self_cache=None) -> torch.Tensor:
+        """The decoder stack on ``tokens`` [B, L] (teacher forcing) -> the final LayerNorm's output [B * L, D] bf16.  The prefill
+        of :meth:`generate` passes ``cross_kv`` [layers, B * S, 2 D] (read instead of projecting the encoder output again) and
+        ``self_cache`` [layers, B, cap, 2 D] (receives each layer's self-attention k|v rows)."""
         cfg = self.config
         B, S, D = enc.shape
         if tokens.shape[0] != B:
@@ -268,13 +342,16 @@ class WhisperSeq2Seq:
                 p = f"layers.{l}."
                 # causal self-attention: q | k | v in one product, the attention reads its three column blocks in place
                 qkv = self._linear(x, self._w(p + "self_attn.q_proj.weight", 3), self._f(p + "self_attn.q_proj.bias", 3))
+                if self_cache is not None:
+                    self_cache[l, :, :L].copy_(qkv[:, D:].view(B, L, 2 * D))
                 ctx = hip.dec_attention_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, L, L, nh, causal=True, q_offset=0)
                 y = self._linear(ctx, self._w(p + "self_attn.out_proj.weight"), self._f(p + "self_attn.out_proj.bias"))
                 hip.layernorm_fwd(y, h, self._f(p + "encoder_attn_layer_norm.weight"), self._f(p + "encoder_attn_layer_norm.bias"), h2, x)
                 h, h2 = h2, h
                 # cross-attention: the layer's k | v projection of the encoder output, [B * S, 2 D]
                 q = self._linear(x, self._w(p + "encoder_attn.q_proj.weight"), self._f(p + "encoder_attn.q_proj.bias"))
-                kv = self._linear(enc2, self._w(p + "encoder_attn.k_proj.weight", 2), self._f(p + "encoder_attn.k_proj.bias", 2))
+                kv = cross_kv[l] if cross_kv is not None else self._linear(enc2, self._w(p + "encoder_attn.k_proj.weight", 2),
+                                                                          self._f(p + "encoder_attn.k_proj.bias", 2))
                 ctx = hip.dec_attention_fwd(q, kv[:, :D], kv[:, D:], B, L, S, nh, klens=enc_lens)
                 y = self._linear(ctx, self._w(p + "encoder_attn.out_proj.weight"), self._f(p + "encoder_attn.out_proj.bias"))
                 hip.layernorm_fwd(y, h, self._f(p + "final_layer_norm.weight"), self._f(p + "final_layer_norm.bias"), h2, x)
@@ -363,10 +440,14 @@ class WhisperSeq2Seq:
         if not len(self.lang_ids):
             raise ValueError("the model folder lists no language tokens (generation_config.json lang_to_id, or <|xx|> entries of "
                              "added_tokens.json / vocab.json): an English-only model has no language to detect")
-        enc = self._as_enc(enc_or_audio)
+        return self._detect_language(self._as_enc(enc_or_audio), enc_lens)
+
+    def _detect_language(self, enc: torch.Tensor, enc_lens=None, cross_kv=None):
+        """:meth:`detect_language` on an encoder output; ``cross_kv``: the cross k|v buffer of a :meth:`generate` call, read
+        instead of projecting the encoder output once more."""
         B = enc.shape[0]
         sot = np.full((B, 1), self.config.decoder_start_token_id, dtype=np.int64)
-        x = self._decoder_hidden(enc, sot, enc_lens)
+        x = self._decoder_hidden(enc, sot, enc_lens, cross_kv=cross_kv)
         with torch.cuda.device(self.device):
             parts = []
             chunk = min(self.row_chunk, B)
@@ -397,3 +478,209 @@ class WhisperSeq2Seq:
         for b, i in enumerate(ids):
             pad[b, :len(i)] = i
         return self.score(enc_or_audio, pad, [len(i) for i in ids])
+
+    # ------------------------------------------------------------------ generation
+    def _gen_begin(self, enc: torch.Tensor, enc_lens=None, cap: Optional[int] = None, step_cross: bool = True,
+                   step_self_min_keys: Optional[int] = STEP_SELF_MIN_KEYS) -> _GenState:
+        """Everything a call computes once: the twelve cross k|v projections of the encoder output into ONE [layers, B * S, 2 D]
+        buffer (1.77 GB at whisper-small, B = 32), the empty self-attention cache, the encoder lengths (validated here, uploaded
+        here, read by the kernels from the device ever after)."""
+        cfg = self.config
+        B, S, D = enc.shape
+        cap = cfg.max_target_positions if cap is None else int(cap)
+        lens_host = lens_dev = None
+        if enc_lens is not None:
+            lens_host = hip._host_i32(enc_lens, B, "enc_lens")
+            if lens_host.min() < 1 or lens_host.max() > S:
+                raise ValueError(f"enc_lens: {B} values in [1, {S}] expected, got {lens_host}")
+            lens_dev = torch.from_numpy(lens_host).to(self.device)
+        with torch.cuda.device(self.device):
+            nl, nh = cfg.decoder_layers, cfg.decoder_attention_heads
+            cross_kv = torch.empty((nl, B * S, 2 * D), dtype=torch.bfloat16, device=self.device)
+            enc2 = enc.reshape(B * S, D)
+            for l in range(nl):
+                p = f"layers.{l}.encoder_attn.k_proj."
+                hip.gemm(enc2, self._w(p + "weight", 2), cross_kv[l], B * S, 2 * D, D, lda=D, ldb=D, ldc=2 * D, bias=self._f(p + "bias", 2))
+            bf = lambda n: torch.empty((B, n), dtype=torch.bfloat16, device=self.device)
+            return _GenState(B=B, S=S, D=D, cap=cap, enc=enc, enc_lens=lens_dev, enc_lens_host=lens_host, cross_kv=cross_kv,
+                             self_kv=torch.zeros((nl, B, cap, 2 * D), dtype=torch.bfloat16, device=self.device),
+                             ws=hip.dec_attention_step_workspace(B, nh, 0, self.device), h=bf(D), h2=bf(D), x=bf(D), q=bf(D), ctx=bf(D), y=bf(D),
+                             f=bf(cfg.decoder_ffn_dim), step_cross=bool(step_cross), step_self_min_keys=step_self_min_keys)
+
+    def _gen_prefill(self, st: _GenState, prompt: np.ndarray) -> torch.Tensor:
+        """One teacher-forced pass over ``prompt`` [B, P] at positions 0 .. P - 1 (``ssak_dec_attention_fwd``, causal), its
+        self-attention k|v into the cache -> the logits [B, Vp] fp32 of the LAST prompt row only."""
+        B, P = prompt.shape
+        if st.t != 0 or P > st.cap:
+            raise ValueError(f"prefill of {P} tokens into a cache of {st.cap} rows with {st.t} in use")
+        x = self._decoder_hidden(st.enc, prompt, st.enc_lens_host, 0, cross_kv=st.cross_kv, self_cache=st.self_kv)
+        st.t = P
+        with torch.cuda.device(self.device):
+            return self._project(x.view(B, P, st.D)[:, P - 1].contiguous(), B)
+
+    def _gen_attend(self, st: _GenState, kind: str, q, kv, n_keys: int):
+        """ctx [B, D] of the one new row: ``kv`` [B, rows, 2 D] is a layer's cache (``kind`` "self": the first ``n_keys`` rows
+        are in use) or its cross k|v ("cross": all S rows, the encoder lengths on top)."""
+        D, nh = st.D, self.config.decoder_attention_heads
+        if st.step_cross if kind == "cross" else (st.step_self_min_keys is not None and n_keys >= st.step_self_min_keys):
+            return hip.dec_attention_step(q, kv[:, :, :D], kv[:, :, D:], n_keys, nh, klens=st.enc_lens if kind == "cross" else None,
+                                          workspace=st.ws, ctx=st.ctx)
+        rows = kv.shape[1]
+        kv2 = kv.reshape(st.B * rows, 2 * D)
+        if kind == "self":  # the causal mask of a query at position n_keys - 1 hides the unused rows of the cache
+            return hip.dec_attention_fwd(q, kv2[:, :D], kv2[:, D:], st.B, 1, rows, nh, causal=True, q_offset=n_keys - 1, ctx=st.ctx)
+        return hip.dec_attention_fwd(q, kv2[:, :D], kv2[:, D:], st.B, 1, rows, nh, klens=st.enc_lens_host, ctx=st.ctx)
+
+    def _gen_step(self, st: _GenState, h_in: torch.Tensor) -> torch.Tensor:
+        """One token: ``h_in`` [B, D] bf16, the embedding row at position ``st.t`` (``ssak_dec_greedy_step``'s ``h_next``), through
+        the layers against the cache and the cross buffer -> the logits [B, Vp] fp32 of that position.  Nothing is read back."""
+        cfg = self.config
+        B, D, F, t = st.B, st.D, cfg.decoder_ffn_dim, st.t
+        if t >= st.cap:
+            raise ValueError(f"the cache of {st.cap} rows is full")
+        lin = lambda a, w, bias, out, N, K, epi=hip.EPI_NONE: hip.gemm(a, w, out, B, N, K, lda=K, ldb=K, ldc=N, bias=bias, epilogue=epi)
+        with torch.cuda.device(self.device):
+            h, h2, x = st.h, st.h2, st.x
+            h.copy_(h_in)
+            hip.layernorm_fwd(None, h, self._f("layers.0.self_attn_layer_norm.weight"), self._f("layers.0.self_attn_layer_norm.bias"), None, x)
+            for l in range(cfg.decoder_layers):
+                p = f"layers.{l}."
+                w3, b3 = self._w(p + "self_attn.q_proj.weight", 3), self._f(p + "self_attn.q_proj.bias", 3)
+                lin(x, w3[:D], b3[:D], st.q, D, D)
+                # the new row's k | v straight into row t of the layer's cache: C's row stride is one utterance's cache
+                hip.gemm(x, w3[D:], st.self_kv[l, :, t], B, 2 * D, D, lda=D, ldb=D, ldc=st.cap * 2 * D, bias=b3[D:])
+                ctx = self._gen_attend(st, "self", st.q, st.self_kv[l], t + 1)
+                lin(ctx, self._w(p + "self_attn.out_proj.weight"), self._f(p + "self_attn.out_proj.bias"), st.y, D, D)
+                hip.layernorm_fwd(st.y, h, self._f(p + "encoder_attn_layer_norm.weight"), self._f(p + "encoder_attn_layer_norm.bias"), h2, x)
+                h, h2 = h2, h
+                lin(x, self._w(p + "encoder_attn.q_proj.weight"), self._f(p + "encoder_attn.q_proj.bias"), st.q, D, D)
+                ctx = self._gen_attend(st, "cross", st.q, st.cross_kv[l].view(B, st.S, 2 * D), st.S)
+                lin(ctx, self._w(p + "encoder_attn.out_proj.weight"), self._f(p + "encoder_attn.out_proj.bias"), st.y, D, D)
+                hip.layernorm_fwd(st.y, h, self._f(p + "final_layer_norm.weight"), self._f(p + "final_layer_norm.bias"), h2, x)
+                h, h2 = h2, h
+                lin(x, self._w(p + "fc1.weight"), self._f(p + "fc1.bias"), st.f, F, D, hip.EPI_GELU)
+                lin(st.f, self._w(p + "fc2.weight"), self._f(p + "fc2.bias"), st.y, D, F)
+                nxt = f"layers.{l + 1}.self_attn_layer_norm." if l + 1 < cfg.decoder_layers else "layer_norm."
+                hip.layernorm_fwd(st.y, h, self._f(nxt + "weight"), self._f(nxt + "bias"), h2, x)
+                h, h2 = h2, h
+            st.h, st.h2 = h, h2
+            st.t = t + 1
+            return self._project(x, B)
+
+    def _token_mask(self, ids, what: str) -> Optional[torch.Tensor]:
+        """A list of token ids -> the uint8 [V] device mask ``ssak_dec_greedy_step`` reads (None for an empty list)."""
+        V = self.config.vocab_size
+        ids = np.asarray([] if ids is None else list(ids), dtype=np.int64).reshape(-1)
+        if not ids.size:
+            return None
+        if ids.min() < 0 or ids.max() >= V:
+            raise ValueError(f"{what}: ids outside [0, {V})")
+        m = np.zeros(V, dtype=np.uint8)
+        m[ids] = 1
+        return torch.from_numpy(m).to(self.device)
+
+    def default_prompt(self, B: int, language=None, task: str = "transcribe") -> np.ndarray:
+        """``[<|startoftranscript|>, language, task, <|notimestamps|>]`` per utterance, [B, 4] (``language``: one code or B codes;
+        a model without language tokens gets ``[<|startoftranscript|>, <|notimestamps|>]``)."""
+        cfg = self.config
+        if cfg.no_timestamps_token_id is None:
+            raise ValueError("the model folder names no no_timestamps_token_id (generation_config.json): pass prompt=")
+        codes = cfg.lang_to_id or {}
+        if not codes:
+            return np.tile(np.array([[cfg.decoder_start_token_id, cfg.no_timestamps_token_id]], dtype=np.int64), (B, 1))
+        if language is None:
+            raise ValueError("default_prompt needs the language (one code or one per utterance); generate() detects it when none is given")
+        langs = [language] * B if isinstance(language, str) else list(language)
+        if len(langs) != B:
+            raise ValueError(f"{len(langs)} languages for {B} utterances")
+        for c in langs:
+            if c not in codes:
+                raise ValueError(f"language {c!r}: the model knows {sorted(codes)}")
+        if not cfg.task_to_id or task not in cfg.task_to_id:
+            raise ValueError(f"task {task!r}: the model folder's task_to_id is {cfg.task_to_id}")
+        return np.array([[cfg.decoder_start_token_id, codes[c], cfg.task_to_id[task], cfg.no_timestamps_token_id] for c in langs], dtype=np.int64)
+
+    def generate(self, enc_or_audio, prompt=None, language=None, task: str = "transcribe", max_new_tokens: Optional[int] = None, enc_lens=None,
+                 suppress_tokens=None, begin_suppress_tokens=None, eos_token_id: Optional[int] = None, poll_every: int = 8) -> GenerateResult:
+        """Greedy transcription (temperature 0, no beam, no timestamps) of a batch in lock step -> :class:`GenerateResult`.
+
+        ``prompt`` [B, P] or [P] ids (one P for the batch); by default ``[<|startoftranscript|>, language, task,
+        <|notimestamps|>]``, where ``language = None`` runs :meth:`detect_language`'s pass first (on this call's cross k|v buffer) and gives each
+        utterance its own token.
+        ``max_new_tokens``: by default what fits, ``max_target_positions - P``; more is a ``ValueError``.  ``suppress_tokens`` /
+        ``begin_suppress_tokens`` / ``eos_token_id`` override the model folder's ``generation_config.json``.  ``enc_lens`` [B]:
+        the encoder frames cross-attention may see.
+
+        Memory: every layer's cross k|v projection of the encoder output is computed ONCE per call into a [layers, B * S, 2 D]
+        bf16 buffer -- 1.77 GB at whisper-small with B = 32 -- next to the [layers, B, P + max_new_tokens, 2 D] cache.
+        The host reads nothing per token: every ``poll_every`` steps it reads the count of unfinished utterances through a pinned
+        word and stops at 0 (``poll_every = 0``: never, the loop runs ``max_new_tokens`` steps); tokens and log-probabilities
+        are copied once at the end."""
+        cfg = self.config
+        enc = self._as_enc(enc_or_audio)
+        B = enc.shape[0]
+        V, maxp = cfg.vocab_size, cfg.max_target_positions
+        eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
+        if eos is None:
+            raise ValueError("no eos_token_id: the model folder names none, pass eos_token_id=")
+        pad = eos if cfg.pad_token_id is None else int(cfg.pad_token_id)
+        # the language pass of the default prompt reads the call's cross k|v buffer, so the prompt is built after _gen_begin;
+        # its width is known before: [<|startoftranscript|>, language, task, <|notimestamps|>]
+        detect = prompt is None and language is None and bool(cfg.lang_to_id)
+        if detect:
+            if not cfg.task_to_id or task not in cfg.task_to_id or cfg.no_timestamps_token_id is None:
+                raise ValueError(f"task {task!r} / no_timestamps_token_id: the model folder's generation_config.json names neither: pass prompt=")
+            P = 4
+        else:
+            if prompt is None:
+                prompt = self.default_prompt(B, language, task)
+            prompt = np.asarray(prompt.cpu() if torch.is_tensor(prompt) else prompt, dtype=np.int64)
+            prompt = np.ascontiguousarray(np.broadcast_to(prompt, (B, prompt.shape[-1])) if prompt.ndim == 1 else prompt)
+            if prompt.ndim != 2 or prompt.shape[0] != B or prompt.shape[1] < 1:
+                raise ValueError(f"prompt [B, P] or [P] for {B} utterances, got shape {prompt.shape}")
+            P = prompt.shape[1]
+        n_max = maxp - P if max_new_tokens is None else int(max_new_tokens)
+        if n_max < 1 or P + n_max > maxp:
+            raise ValueError(f"prompt of {P} + max_new_tokens {n_max} tokens: the decoder has max_target_positions = {maxp} positions")
+        if poll_every < 0:
+            raise ValueError("poll_every must be >= 0")
+        sup = self._token_mask(cfg.suppress_tokens if suppress_tokens is None else suppress_tokens, "suppress_tokens")
+        bsup = self._token_mask(cfg.begin_suppress_tokens if begin_suppress_tokens is None else begin_suppress_tokens, "begin_suppress_tokens")
+        st = self._gen_begin(enc, enc_lens, cap=P + n_max)
+        if detect:
+            prompt = self.default_prompt(B, self._detect_language(enc, st.enc_lens_host, cross_kv=st.cross_kv)[0], task)
+        logits = self._gen_prefill(st, prompt)
+        E, Pz = self._w("embed_tokens.weight"), self._w("embed_positions.weight")
+        with torch.cuda.device(self.device):
+            tokens = torch.full((B, n_max), pad, dtype=torch.int32, device=self.device)
+            logprobs = torch.zeros((B, n_max), dtype=torch.float32, device=self.device)
+            finished = torch.zeros(B, dtype=torch.uint8, device=self.device)
+            n_unf = torch.zeros(1, dtype=torch.int32, device=self.device)
+            word = torch.zeros(1, dtype=torch.int32).pin_memory()
+            h_next = torch.empty((B, st.D), dtype=torch.bfloat16, device=self.device)
+            steps = 0
+            for i in range(n_max):
+                last = i + 1 == n_max
+                hip.dec_greedy_step(logits, V, finished=finished, n_unfinished=n_unf, tokens=tokens, logprobs=logprobs, t=i, eos_id=eos, pad_id=pad,
+                                    suppress=sup, begin_suppress=bsup, first=i == 0, embed_tokens=E, embed_positions=Pz, next_pos=P + i,
+                                    h_next=None if last else h_next)
+                steps = i + 1
+                if last:
+                    break
+                if poll_every and steps % poll_every == 0:
+                    word.copy_(n_unf, non_blocking=True)
+                    torch.cuda.current_stream().synchronize()
+                    if int(word[0]) == 0:
+                        break
+                logits = self._gen_step(st, h_next)
+            tok = tokens[:, :steps].cpu().numpy()
+            lp = logprobs[:, :steps].double().cpu().numpy()
+        lens = np.array([int(np.argmax(r == eos)) + 1 if (r == eos).any() else steps for r in tok], dtype=np.int64)
+        n = int(lens.max())
+        tok, lp = tok[:, :n].copy(), lp[:, :n].copy()
+        for b in range(B):  # (a finished row emits pad with log-probability 0 already; this also covers pad == eos)
+            tok[b, lens[b]:] = pad
+            lp[b, lens[b]:] = 0.0
+        s = lp.sum(-1)
+        return GenerateResult(tokens=[tok[b, :lens[b]].tolist() for b in range(B)], lens=lens, token_array=tok, logprobs=lp, sum_logprob=s,
+                              avg_logprob=s / (lens + 1), steps=steps)
