@@ -754,6 +754,29 @@ int ssak_dec_greedy_step(const float* logits, long ldv, int B, int V, const uint
                          const void* embed_tokens, const void* embed_positions, int D, int max_positions, int next_pos, int eos_id, int pad_id,
                          uint8_t* finished, int32_t* n_unfinished, int32_t* tokens, float* logprobs, long ldt, int t, void* h_next,
                          void* stream);
+/* ---- Whisper timestamps (ABI 620): the token selection of a step under whisper's ApplyTimestampRules ---------------------
+ * ssak_dec_timestamp_step.  ssak_dec_greedy_step -- the same outputs and conventions: tokens and log-probs at column t, finished,
+ * n_unfinished, h_next, the two suppress masks and `first`, the lowest id on a tie, fixed-order sums, integer atomics only --
+ * with the rules of whisper/decoding.py ApplyTimestampRules (transformers' WhisperTimeStampLogitsProcessor) applied on the
+ * device, so the generation loop still reads nothing back per token.  ts_begin = the first timestamp id (no_timestamps_id + 1 in
+ * Whisper's vocabularies), max_initial = the largest allowed index of the first timestamp (< 0: none), ts_last [B] int32 on the
+ * device = the row's most recent sampled timestamp id or -1: at t == 0 the kernel does not read it and writes it, later it reads
+ * it and updates it when it emits a timestamp (a finished row's entry is left alone).  The row's history is the n = t tokens
+ * the kernel itself wrote at tokens[b * ldt + 0 .. t - 1]; of these it reads the last two.  With
+ *     last = n >= 1 && tok[t - 1] >= ts_begin,   pen = n < 2 || tok[t - 2] >= ts_begin,
+ * a column is allowed unless: a suppress mask hits it; it is no_timestamps_id; last && pen and it is a timestamp; last && !pen
+ * and it is < eos_id; ts_last >= 0 and it lies in [ts_begin, floor) with floor = ts_last if last && !pen, else ts_last + 1;
+ * n == 0 and it is < ts_begin, or > ts_begin + max_initial when max_initial >= 0.  Over the allowed columns: M = the maximum,
+ * S_text / S_ts = the sums of exp(x - M) over the columns below / from ts_begin, m_text = the largest text logit.  If S_ts > 0
+ * and log S_ts > m_text - M (the timestamps together outweigh every single text token) the text columns are masked as well:
+ * token = the lowest timestamp arg-max, logprob = (x_token - M) - log S_ts.  Otherwise token = the lowest arg-max over all
+ * allowed columns, logprob = (x_token - M) - log(S_text + S_ts).  A row with no allowed column emits pad_id with log-prob 0.
+ * ts_begin <= eos_id, ts_begin >= V, no_timestamps_id outside [0, V), a NULL ts_last, and everything ssak_dec_greedy_step
+ * refuses: SSAK_ERR_INVALID, nothing launched. */
+int ssak_dec_timestamp_step(const float* logits, long ldv, int B, int V, const uint8_t* suppress, const uint8_t* begin_suppress, int first,
+                            int ts_begin, int no_timestamps_id, int max_initial, const void* embed_tokens, const void* embed_positions, int D,
+                            int max_positions, int next_pos, int eos_id, int pad_id, uint8_t* finished, int32_t* n_unfinished,
+                            int32_t* tokens, float* logprobs, long ldt, int t, int32_t* ts_last, void* h_next, void* stream);
 /* r = res + y (either may be NULL) -> r_out (may be NULL), out = LayerNorm(r) * gamma + beta (may be NULL) on [M, C] rows of
  * dtype 0 = bf16 / 1 = fp32: the row kernel of the encoder layers without dropout sites or saved statistics.  C a multiple of
  * 8, <= 1536. */

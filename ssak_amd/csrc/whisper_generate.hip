@@ -1,4 +1,4 @@
-// The Whisper generation loop's own kernels (ABI 610): the attention of ONE query per (utterance, head) against a key / value
+// The Whisper generation loop's own kernels (ABI 610, 620): the attention of ONE query per (utterance, head) against a key / value
 // cache, and the token selection that closes a step and forms the next step's input row.  Neither entry takes a host copy of a
 // device array: the loop of ssak_amd/whisper_seq2seq.py (`generate`) stays on the device between tokens.
 //
@@ -17,6 +17,13 @@
 //
 // dec_greedy_kernel.  One workgroup per row, the two-pass shape of token_logprobs_kernel with the suppress masks applied as the
 // columns are read.
+//
+// dec_timestamp_kernel (ABI 620).  dec_greedy_kernel with whisper's ApplyTimestampRules folded into the column predicate.  The
+// rules of a row reduce to uniform scalars read before the loop -- the two tokens the kernel itself wrote at columns t - 1 and
+// t - 2, and ts_last[b] -- that give one text interval [text_lo, ts_begin) and one timestamp interval [ts_lo, ts_hi]; a column
+// is allowed when no mask byte hits it, it is not <|notimestamps|> and it lies in one of the two.  No per-row mask exists in
+// memory.  Pass one carries four running statistics per thread (the text and the timestamp maximum, each with its lowest
+// column), pass two the two sums of exp(x - M) in column order; lanes, then waves, in a fixed order.
 #include <limits.h>
 
 #include <algorithm>
@@ -298,6 +305,157 @@ __global__ __launch_bounds__(GS_THREADS) void dec_greedy_kernel(const GsParams p
     }
   }
 }
+
+// ---- ssak_dec_timestamp_step -------------------------------------------------------------------------------------------------
+struct TsParams {
+  GsParams g;
+  int32_t* ts_last;
+  int ts_begin, no_timestamps_id, max_initial;
+};
+
+// (value, lowest column) of the maximum over the workgroup: lanes, then waves; every thread returns the same pair
+__device__ __forceinline__ void block_argmax(float& best, int32_t& bi, float* red, int32_t* ired) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float ov = __shfl_xor(best, o);
+    const int32_t oi = __shfl_xor(bi, o);
+    if (ov > best || (ov == best && oi < bi)) {
+      best = ov;
+      bi = oi;
+    }
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = best;
+    ired[threadIdx.x >> 6] = bi;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ww = 0; ww < GS_THREADS / 64; ++ww) {
+    const float ov = red[ww];
+    const int32_t oi = ired[ww];
+    if (ov > best || (ov == best && oi < bi)) {
+      best = ov;
+      bi = oi;
+    }
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(GS_THREADS) void dec_timestamp_kernel(const TsParams q) {
+  __shared__ float red[16];
+  __shared__ int32_t ired[16];
+  const GsParams& p = q.g;
+  const int tid = threadIdx.x, row = blockIdx.x;
+  const float* x = p.logits + (long)row * p.ldv;
+  const uint8_t* const s0 = p.suppress;
+  const uint8_t* const s1 = p.begin_suppress;
+  const bool was_finished = p.finished[row] != 0;  // (read by every thread before thread 0 writes it, behind the barriers below)
+  int token = p.pad_id;
+  float logprob = 0.f;
+  int ts_new = -1;  // what ts_last[row] becomes; only an unfinished row writes it
+  if (!was_finished) {  // (uniform over the workgroup)
+    const int V = p.V, n = p.t, tsb = q.ts_begin;
+    const int32_t* const hist = p.tokens + (long)row * p.ldt;
+    const bool last = n >= 1 && hist[n - 1] >= tsb;
+    const bool pen = n < 2 || hist[n - 2] >= tsb;
+    const int ts_prev = n == 0 ? -1 : q.ts_last[row];  // (every thread reads it before thread 0 writes it, behind the barriers below)
+    ts_new = ts_prev;
+    // the rules as two intervals: text columns [text_lo, tsb), timestamp columns [ts_lo, ts_hi]
+    const int text_lo = n == 0 ? tsb : (last && !pen ? p.eos_id : 0);
+    int ts_lo = tsb, ts_hi = V - 1;
+    if (ts_prev >= 0) ts_lo = max(ts_lo, last && !pen ? ts_prev : ts_prev + 1);
+    if (n == 0 && q.max_initial >= 0) ts_hi = min((long)ts_hi, (long)tsb + q.max_initial);
+    if (last && pen) ts_hi = -1;
+    const int nots = q.no_timestamps_id;
+    const auto allowed = [&](int c) { return c != nots && ((c >= text_lo && c < tsb) || (c >= ts_lo && c <= ts_hi)); };
+
+    const int n4 = VEC ? (V & ~3) : 0;
+    float mt = -INFINITY, ms = -INFINITY;  // the text maximum, the timestamp maximum
+    int32_t it = INT_MAX, is = INT_MAX;
+    for (int i = tid * 4; i < n4; i += GS_THREADS * 4) {
+      const float4 f = *reinterpret_cast<const float4*>(x + i);
+      uint32_t mk = s0 ? *reinterpret_cast<const uint32_t*>(s0 + i) : 0u;
+      if (s1) mk |= *reinterpret_cast<const uint32_t*>(s1 + i);
+      const float v[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = i + e;
+        if (((mk >> (8 * e)) & 0xffu) || !allowed(c)) continue;
+        if (c < tsb) {
+          if (v[e] > mt) mt = v[e], it = c;  // strict: within a thread's increasing columns the first maximum stays
+        } else if (v[e] > ms) {
+          ms = v[e], is = c;
+        }
+      }
+    }
+    for (int i = n4 + tid; i < V; i += GS_THREADS) {
+      const bool sup = (s0 && s0[i]) || (s1 && s1[i]);
+      const float v = x[i];
+      if (sup || !allowed(i)) continue;
+      if (i < tsb) {
+        if (v > mt || (v == mt && i < it)) mt = v, it = i;
+      } else if (v > ms || (v == ms && i < is)) {
+        ms = v, is = i;
+      }
+    }
+    block_argmax(mt, it, red, ired);
+    block_argmax(ms, is, red, ired);
+    const float M = fmaxf(mt, ms);
+    if (it < V || is < V) {  // (a row with no allowed column, the caller's error, emits pad_id with log-prob 0)
+      float st = 0.f, ss = 0.f;  // sums of exp(x - M) over the allowed text / timestamp columns
+      for (int i = tid * 4; i < n4; i += GS_THREADS * 4) {
+        const float4 f = *reinterpret_cast<const float4*>(x + i);
+        uint32_t mk = s0 ? *reinterpret_cast<const uint32_t*>(s0 + i) : 0u;
+        if (s1) mk |= *reinterpret_cast<const uint32_t*>(s1 + i);
+        const float v[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int c = i + e;
+          const float ex = (((mk >> (8 * e)) & 0xffu) || !allowed(c)) ? 0.f : expf(v[e] - M);
+          st += c < tsb ? ex : 0.f;
+          ss += c < tsb ? 0.f : ex;
+        }
+      }
+      for (int i = n4 + tid; i < V; i += GS_THREADS) {
+        const bool sup = (s0 && s0[i]) || (s1 && s1[i]);
+        const float ex = (sup || !allowed(i)) ? 0.f : expf(x[i] - M);
+        st += i < tsb ? ex : 0.f;
+        ss += i < tsb ? 0.f : ex;
+      }
+      st = block_sum(st, red);
+      ss = block_sum(ss, red);
+      // the timestamps' mass against the likeliest text token: log S_ts - log S > m_text - M - log S
+      if (ss > 0.f && logf(ss) > mt - M) {
+        token = is;
+        logprob = (ms - M) - logf(ss);
+      } else {
+        token = (it < V && mt >= ms) ? it : is;  // (text ids lie below the timestamps: the lowest id on a tie)
+        logprob = -logf(st + ss);                // x[token] = M
+      }
+      if (token >= tsb) ts_new = token;
+    }
+  }
+  if (tid == 0) {
+    p.tokens[(long)row * p.ldt + p.t] = token;
+    p.logprobs[(long)row * p.ldt + p.t] = logprob;
+    const bool now_finished = was_finished || token == p.eos_id;
+    p.finished[row] = now_finished ? 1 : 0;
+    if (!was_finished) q.ts_last[row] = ts_new;
+    if (!now_finished) atomicAdd(p.n_unfinished, 1);  // (an integer count on the word the entry zeroed: order-free)
+  }
+  if (p.h_next) {
+    const int id = min(max(token, 0), p.V - 1);
+    for (int ch = tid; ch < (p.D >> 3); ch += GS_THREADS) {
+      float e[8], r[8];
+      chunk_to_f(ld8<bf16>(p.embed_tokens + (long)id * p.D + ch * 8), e);
+      chunk_to_f(ld8<bf16>(p.embed_positions + (long)p.next_pos * p.D + ch * 8), r);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) e[k] += r[k];
+      st8<bf16>(p.h_next + (long)row * p.D + ch * 8, f_to_chunk8<bf16>(e));
+    }
+  }
+}
 }  // namespace
 
 extern "C" size_t ssak_dec_attention_step_workspace_bytes(int B, int nh, int n_split) {
@@ -349,33 +507,70 @@ extern "C" int ssak_dec_attention_step(const void* q, long ldq, const void* k, l
   return SSAK_OK;
 }
 
-extern "C" int ssak_dec_greedy_step(const float* logits, long ldv, int B, int V, const uint8_t* suppress, const uint8_t* begin_suppress,
-                                    int first, const void* embed_tokens, const void* embed_positions, int D, int max_positions, int next_pos,
-                                    int eos_id, int pad_id, uint8_t* finished, int32_t* n_unfinished, int32_t* tokens, float* logprobs,
-                                    long ldt, int t, void* h_next, void* stream) {
-  SSAK_REQUIRE(logits && finished && n_unfinished && tokens && logprobs, "dec_greedy_step: null pointer");
-  SSAK_REQUIRE(B > 0 && V > 0 && ldv >= V, "dec_greedy_step: bad shape B=%d V=%d ldv=%ld", B, V, ldv);
-  SSAK_REQUIRE(eos_id >= 0 && eos_id < V && pad_id >= 0 && pad_id < V, "dec_greedy_step: eos_id=%d / pad_id=%d outside [0, %d)", eos_id, pad_id, V);
-  SSAK_REQUIRE(t >= 0 && t < ldt, "dec_greedy_step: step t=%d outside the token buffer's %ld columns", t, ldt);
+namespace {
+// what ssak_dec_greedy_step and ssak_dec_timestamp_step refuse alike; fills the shared parameters
+int greedy_params(const char* who, const float* logits, long ldv, int B, int V, const uint8_t* suppress, const uint8_t* begin_suppress, int first,
+                  const void* embed_tokens, const void* embed_positions, int D, int max_positions, int next_pos, int eos_id, int pad_id,
+                  uint8_t* finished, int32_t* n_unfinished, int32_t* tokens, float* logprobs, long ldt, int t, void* h_next, GsParams* out) {
+  SSAK_REQUIRE(logits && finished && n_unfinished && tokens && logprobs, "%s: null pointer", who);
+  SSAK_REQUIRE(B > 0 && V > 0 && ldv >= V, "%s: bad shape B=%d V=%d ldv=%ld", who, B, V, ldv);
+  SSAK_REQUIRE(eos_id >= 0 && eos_id < V && pad_id >= 0 && pad_id < V, "%s: eos_id=%d / pad_id=%d outside [0, %d)", who, eos_id, pad_id, V);
+  SSAK_REQUIRE(t >= 0 && t < ldt, "%s: step t=%d outside the token buffer's %ld columns", who, t, ldt);
   if (h_next) {
-    SSAK_REQUIRE(embed_tokens && embed_positions, "dec_greedy_step: h_next needs the two embedding tables");
-    SSAK_REQUIRE(D > 0 && D % 8 == 0 && max_positions > 0, "dec_greedy_step: bad shape D=%d max_positions=%d", D, max_positions);
-    SSAK_REQUIRE(next_pos >= 0 && next_pos < max_positions, "dec_greedy_step: next_pos=%d overruns the position table of %d", next_pos,
-                 max_positions);
-    SSAK_REQUIRE(aligned16(embed_tokens) && aligned16(embed_positions) && aligned16(h_next), "dec_greedy_step: a buffer is not 16-byte aligned");
+    SSAK_REQUIRE(embed_tokens && embed_positions, "%s: h_next needs the two embedding tables", who);
+    SSAK_REQUIRE(D > 0 && D % 8 == 0 && max_positions > 0, "%s: bad shape D=%d max_positions=%d", who, D, max_positions);
+    SSAK_REQUIRE(next_pos >= 0 && next_pos < max_positions, "%s: next_pos=%d overruns the position table of %d", who, next_pos, max_positions);
+    SSAK_REQUIRE(aligned16(embed_tokens) && aligned16(embed_positions) && aligned16(h_next), "%s: a buffer is not 16-byte aligned", who);
   }
-  const hipStream_t st = (hipStream_t)stream;
-  GsParams p;
+  GsParams& p = *out;
   p.logits = logits, p.suppress = suppress, p.begin_suppress = first ? begin_suppress : nullptr;
   p.embed_tokens = (const bf16*)embed_tokens, p.embed_positions = (const bf16*)embed_positions;
   p.finished = finished, p.n_unfinished = n_unfinished, p.tokens = tokens, p.logprobs = logprobs, p.h_next = (bf16*)h_next;
   p.ldv = ldv, p.ldt = ldt, p.V = V, p.D = D, p.t = t, p.next_pos = next_pos, p.eos_id = eos_id, p.pad_id = pad_id;
+  return SSAK_OK;
+}
+bool greedy_vec(const GsParams& p) {
+  return aligned16(p.logits) && p.ldv % 4 == 0 && ((uintptr_t)p.suppress & 3) == 0 && ((uintptr_t)p.begin_suppress & 3) == 0;
+}
+}  // namespace
+
+extern "C" int ssak_dec_greedy_step(const float* logits, long ldv, int B, int V, const uint8_t* suppress, const uint8_t* begin_suppress,
+                                    int first, const void* embed_tokens, const void* embed_positions, int D, int max_positions, int next_pos,
+                                    int eos_id, int pad_id, uint8_t* finished, int32_t* n_unfinished, int32_t* tokens, float* logprobs,
+                                    long ldt, int t, void* h_next, void* stream) {
+  GsParams p;
+  const int rc = greedy_params("dec_greedy_step", logits, ldv, B, V, suppress, begin_suppress, first, embed_tokens, embed_positions, D, max_positions,
+                               next_pos, eos_id, pad_id, finished, n_unfinished, tokens, logprobs, ldt, t, h_next, &p);
+  if (rc != SSAK_OK) return rc;
+  const hipStream_t st = (hipStream_t)stream;
   SSAK_HIP(hipMemsetAsync(n_unfinished, 0, sizeof(int32_t), st));
-  const bool vec = aligned16(logits) && ldv % 4 == 0 && ((uintptr_t)suppress & 3) == 0 && ((uintptr_t)begin_suppress & 3) == 0;
-  if (vec)
+  if (greedy_vec(p))
     dec_greedy_kernel<true><<<B, GS_THREADS, 0, st>>>(p);
   else
     dec_greedy_kernel<false><<<B, GS_THREADS, 0, st>>>(p);
+  SSAK_LAUNCH_CHECK();
+  return SSAK_OK;
+}
+
+extern "C" int ssak_dec_timestamp_step(const float* logits, long ldv, int B, int V, const uint8_t* suppress, const uint8_t* begin_suppress,
+                                       int first, int ts_begin, int no_timestamps_id, int max_initial, const void* embed_tokens,
+                                       const void* embed_positions, int D, int max_positions, int next_pos, int eos_id, int pad_id,
+                                       uint8_t* finished, int32_t* n_unfinished, int32_t* tokens, float* logprobs, long ldt, int t,
+                                       int32_t* ts_last, void* h_next, void* stream) {
+  TsParams q;
+  const int rc = greedy_params("dec_timestamp_step", logits, ldv, B, V, suppress, begin_suppress, first, embed_tokens, embed_positions, D,
+                               max_positions, next_pos, eos_id, pad_id, finished, n_unfinished, tokens, logprobs, ldt, t, h_next, &q.g);
+  if (rc != SSAK_OK) return rc;
+  SSAK_REQUIRE(ts_last, "dec_timestamp_step: ts_last is NULL");
+  SSAK_REQUIRE(ts_begin > eos_id && ts_begin < V, "dec_timestamp_step: ts_begin=%d must lie in (eos_id=%d, V=%d)", ts_begin, eos_id, V);
+  SSAK_REQUIRE(no_timestamps_id >= 0 && no_timestamps_id < V, "dec_timestamp_step: no_timestamps_id=%d outside [0, %d)", no_timestamps_id, V);
+  q.ts_last = ts_last, q.ts_begin = ts_begin, q.no_timestamps_id = no_timestamps_id, q.max_initial = max_initial < 0 ? -1 : max_initial;
+  const hipStream_t st = (hipStream_t)stream;
+  SSAK_HIP(hipMemsetAsync(n_unfinished, 0, sizeof(int32_t), st));
+  if (greedy_vec(q.g))
+    dec_timestamp_kernel<true><<<B, GS_THREADS, 0, st>>>(q);
+  else
+    dec_timestamp_kernel<false><<<B, GS_THREADS, 0, st>>>(q);
   SSAK_LAUNCH_CHECK();
   return SSAK_OK;
 }

@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 610  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 620  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -182,6 +182,8 @@ def _load():
         "ssak_dec_attention_step_workspace_bytes": (sz, [i32, i32, i32]),
         "ssak_dec_attention_step": (i32, [vp, C.c_long, vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, i32, vp, i32, i32, i32, i32, vp, sz, vp, vp]),
         "ssak_dec_greedy_step": (i32, [vp, C.c_long, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_long, i32, vp, vp]),
+        "ssak_dec_timestamp_step": (i32, [vp, C.c_long, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_long,
+                                          i32, vp, vp, vp]),
         "ssak_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]),
         "ssak_debug_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, C.c_long, i32, vp, C.POINTER(f32), vp]),
         "ssak_debug_attention_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, i32, i32, i32, vp, vp]),
@@ -752,7 +754,7 @@ def token_logprobs(logits: torch.Tensor, V: int, targets=None, allowed=None):
     return lse, logprob, argmax, probs
 
 
-# ------------------------------------------------------------------ Whisper generation (ABI 610): no host copies, nothing read back
+# ------------------------------------------------------------------ Whisper generation (ABI 610, 620): no host copies, nothing read back
 def dec_attention_step_workspace(B: int, nh: int, n_split: int = 0, device="cuda:0"):
     """The fp32 workspace of :func:`dec_attention_step` for ``n_split`` pieces (0: enough for any split the library chooses)."""
     return torch.empty(max(lib.ssak_dec_attention_step_workspace_bytes(int(B), int(nh), int(n_split)) // 4, 4), dtype=torch.float32, device=device)
@@ -798,6 +800,31 @@ def dec_greedy_step(logits, V: int, *, finished, n_unfinished, tokens, logprobs,
     check(lib.ssak_dec_greedy_step(ptr(logits), logits.stride(0), B, int(V), ptr(suppress), ptr(begin_suppress), int(bool(first)),
                                    ptr(embed_tokens), ptr(embed_positions), D, max_pos, int(next_pos), int(eos_id), int(pad_id), ptr(finished),
                                    ptr(n_unfinished), ptr(tokens), ptr(logprobs), tokens.shape[1], int(t), ptr(h_next), stream()))
+
+
+def dec_timestamp_step(logits, V: int, *, finished, n_unfinished, tokens, logprobs, t: int, eos_id: int, pad_id: int, ts_begin: int,
+                       no_timestamps_id: int, ts_last, max_initial: int = -1, suppress=None, begin_suppress=None, first: bool = False,
+                       embed_tokens=None, embed_positions=None, next_pos: int = 0, h_next=None):
+    """``ssak_dec_timestamp_step`` (ABI 620): :func:`dec_greedy_step` under whisper's timestamp rules.  ``ts_last``: int32 [B] on the
+    device, the row's most recent timestamp id or -1 (written at ``t == 0``, read and updated afterwards); ``max_initial``: the
+    largest index of the first timestamp, -1 for none.  The history is what the kernel wrote at ``tokens[:, :t]``."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    B = logits.shape[0]
+    assert tokens.dtype == torch.int32 and logprobs.dtype == torch.float32 and tokens.shape == logprobs.shape and tokens.shape[0] == B
+    assert tokens.is_contiguous() and logprobs.is_contiguous()
+    assert finished.dtype == torch.uint8 and finished.numel() == B and n_unfinished.dtype == torch.int32
+    assert ts_last is None or (ts_last.is_cuda and ts_last.dtype == torch.int32 and ts_last.numel() == B and ts_last.is_contiguous())
+    for m in (suppress, begin_suppress):
+        assert m is None or (m.is_cuda and m.dtype == torch.uint8 and m.numel() == V and m.is_contiguous())
+    D = max_pos = 0
+    if h_next is not None:
+        assert embed_tokens.dtype == torch.bfloat16 and embed_tokens.is_contiguous() and embed_positions.is_contiguous()
+        D, max_pos = embed_tokens.shape[1], embed_positions.shape[0]
+        assert h_next.dtype == torch.bfloat16 and h_next.is_contiguous() and tuple(h_next.shape) == (B, D)
+    check(lib.ssak_dec_timestamp_step(ptr(logits), logits.stride(0), B, int(V), ptr(suppress), ptr(begin_suppress), int(bool(first)),
+                                      int(ts_begin), int(no_timestamps_id), int(max_initial), ptr(embed_tokens), ptr(embed_positions), D,
+                                      max_pos, int(next_pos), int(eos_id), int(pad_id), ptr(finished), ptr(n_unfinished), ptr(tokens),
+                                      ptr(logprobs), tokens.shape[1], int(t), ptr(ts_last), ptr(h_next), stream()))
 
 
 def layernorm_fwd(y, res, gamma, beta, r_out=None, out=None, eps: float = 1e-5):

@@ -2,12 +2,17 @@
 ``temperature = 0.0``, ``beam_size = None``, ``condition_on_previous_text = False``)::
 
     python -m ssak_amd.whisper_infer AUDIO... --model DIR [--language fr] [--task transcribe] [--max_new_tokens N] [--batch_size N]
+                                     [--timestamps]
 
 prints one line per file, ``path<TAB>ids`` (the generated token ids, space-separated, without the prompt) and, where
 ``transformers.WhisperTokenizer`` can be imported and ``DIR`` holds a tokenizer, ``<TAB>text``.  ``DIR`` is a
 ``WhisperForConditionalGeneration`` folder in the HuggingFace layout (nothing is downloaded).  Without ``--language`` the language
 of each file is detected first.  Audio goes through the device ingest, Whisper's 30 s window and ``ssak_logmel_whisper``, then
-:meth:`ssak_amd.whisper_seq2seq.WhisperSeq2Seq.generate`.  Audio longer than 30 s is refused by name: no seeking is built.
+:meth:`ssak_amd.whisper_seq2seq.WhisperSeq2Seq.generate`.  Audio longer than 30 s is refused by name unless ``--timestamps`` is given.
+
+``--timestamps`` runs :meth:`ssak_amd.whisper_seq2seq.WhisperSeq2Seq.transcribe` instead -- the timestamp rules, the 30 s window
+seeking through a file of any length, silent windows skipped -- and prints one line per segment,
+``path<TAB>start<TAB>end<TAB>ids[<TAB>text]`` (seconds; the ids without the timestamp tokens).
 """
 from __future__ import annotations
 
@@ -37,15 +42,30 @@ def main(argv=None):
     ap.add_argument("--max_new_tokens", type=int, default=None, metavar="N", help="at most N tokens per file (default: what the decoder's positions hold)")
     ap.add_argument("--batch_size", type=int, default=8, metavar="N", help="files per batch")
     ap.add_argument("--device", default="cuda:0", help="GPU to run on")
+    ap.add_argument("--timestamps", action="store_true", help="long-form transcription with timestamps: any length, one line per segment")
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         ap.error("--batch_size must be at least 1")
+    if args.timestamps and args.max_new_tokens is not None:
+        ap.error("--max_new_tokens does not apply with --timestamps (a window decodes up to half the decoder's positions)")
     model = WhisperSeq2Seq.from_pretrained(args.model, device=args.device)
     tok = _tokenizer(args.model)
     ingest = DeviceIngest(sample_rate=16000, device=args.device, normalize=False)
     for i in range(0, len(args.audio), args.batch_size):
         paths = args.audio[i:i + args.batch_size]
         waves, lens = ingest.load_batch([(p, None, None) for p in paths])
+        if args.timestamps:
+            ns = lens.cpu().tolist() if hasattr(lens, "cpu") else list(lens)
+            ts_begin = model.config.no_timestamps_token_id + 1
+            for path, res in zip(paths, model.transcribe([waves[b, :n] for b, n in enumerate(ns)], language=args.language, task=args.task,
+                                                         batch_size=args.batch_size)):
+                for seg in res.segments:
+                    ids = [t for t in seg.tokens if t < ts_begin]
+                    line = f"{path}\t{seg.start:.2f}\t{seg.end:.2f}\t{' '.join(str(t) for t in ids)}"
+                    if tok is not None:
+                        line += "\t" + tok.decode(ids, skip_special_tokens=True).strip()
+                    print(line)
+            continue
         for path, n in zip(paths, lens.cpu().tolist() if hasattr(lens, "cpu") else list(lens)):
             if n > N_SAMPLES:
                 raise SystemExit(f"{path}: {n / 16000:.1f} s of audio; only the first 30 s window is built (no seeking): cut the file")

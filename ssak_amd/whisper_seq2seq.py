@@ -25,11 +25,16 @@ utterance through the layers -- ``ssak_dec_attention_step`` on the cache and on 
 logits processors, the arg-max, the log-probability, the finished flags and the next input row.  The loop stays on the device:
 the host reads one pinned word every ``poll_every`` steps and the tokens once at the end.
 
+With ``timestamps=True`` the step is ``ssak_dec_timestamp_step`` (whisper's ``ApplyTimestampRules`` on the device) and the call
+also returns ``no_speech_prob``; :meth:`WhisperSeq2Seq.transcribe` (ssak_amd/whisper_transcribe.py) seeks a 30 s window through
+files of any length by the timestamps it predicted, as ``model.transcribe`` does.
+
 Token ids are the contract (no tokenizer is needed, and none is shipped); :meth:`WhisperSeq2Seq.score_text` is a convenience
-that imports ``transformers.WhisperTokenizer`` lazily.  Not built: timestamps, fallback temperatures, beam search,
-``no_speech_prob``, long-form seeking, ``condition_on_previous_text``, a skinny-M GEMM for the token step, hipGraph capture of the
-step, training / LoRA, an fp32-exact mode of the decoder.  Timing: tools/bench_whisper_decoder.py, tools/bench_whisper_generate.py
-(DESIGN.md "Whisper decoder", "Whisper generation").
+that imports ``transformers.WhisperTokenizer`` lazily.  Not built: fallback temperatures and ``compression_ratio_threshold``, beam
+search, ``condition_on_previous_text`` / ``initial_prompt``, word timestamps, a skinny-M GEMM for the token step, hipGraph capture
+of the step, training / LoRA, an fp32-exact mode of the decoder.  Timing: tools/bench_whisper_decoder.py,
+tools/bench_whisper_generate.py, tools/bench_whisper_transcribe.py (DESIGN.md "Whisper decoder", "Whisper generation", "Whisper
+long-form transcription").
 """
 from __future__ import annotations
 
@@ -76,6 +81,10 @@ class WhisperSeq2SeqConfig:
     begin_suppress_tokens: Optional[List[int]] = None
     task_to_id: Optional[Dict[str, int]] = None
     no_timestamps_token_id: Optional[int] = None
+    # what generate(timestamps=True) reads on top: the largest index of a window's first timestamp (None: no limit) and the
+    # <|nospeech|> token (None: no_timestamps_token_id - 1, where Whisper's vocabularies have it)
+    max_initial_timestamp_index: Optional[int] = 50
+    no_speech_token_id: Optional[int] = None
 
     def __post_init__(self):
         for what, heads in (("encoder", self.encoder_attention_heads), ("decoder", self.decoder_attention_heads)):
@@ -115,7 +124,9 @@ class GenerateResult:
     """``tokens``: per utterance the generated ids without the prompt, ending at its ``eos`` if it reached one; ``lens`` [B] their
     counts; ``token_array`` [B, n] int32, the same ids padded with ``pad`` (n = the longest); ``logprobs`` [B, n] float64, each
     token's log-softmax under the processed logits, 0 past ``lens``; ``sum_logprob`` [B]; ``avg_logprob`` = sum / (len + 1) as
-    :class:`ScoreResult` has it; ``steps``: the token steps the loop ran before it stopped."""
+    :class:`ScoreResult` has it; ``steps``: the token steps the loop ran before it stopped.  ``no_speech_prob`` [B] float64 (only
+    with ``timestamps=True``, else None): the softmax probability of the no-speech token on the unprocessed logits of the
+    ``<|startoftranscript|>`` row."""
     tokens: List[List[int]]
     lens: np.ndarray
     token_array: np.ndarray
@@ -123,6 +134,7 @@ class GenerateResult:
     sum_logprob: np.ndarray
     avg_logprob: np.ndarray
     steps: int
+    no_speech_prob: Optional[np.ndarray] = None
 
 
 # The shortest self-attention cache on which the token step runs ssak_dec_attention_step; below it, ssak_dec_attention_fwd at
@@ -261,7 +273,7 @@ class WhisperSeq2Seq:
                 g = json.load(f)
             lang_to_id = g.get("lang_to_id")
             for key in ("decoder_start_token_id", "eos_token_id", "pad_token_id", "suppress_tokens", "begin_suppress_tokens", "task_to_id",
-                        "no_timestamps_token_id"):
+                        "no_timestamps_token_id", "max_initial_timestamp_index", "no_speech_token_id"):
                 if g.get(key) is not None:
                     extra[key] = g[key]
             if isinstance(extra.get("eos_token_id"), list):  # (newer generation configs list several: the first is <|endoftext|>)
@@ -507,16 +519,24 @@ class WhisperSeq2Seq:
                              ws=hip.dec_attention_step_workspace(B, nh, 0, self.device), h=bf(D), h2=bf(D), x=bf(D), q=bf(D), ctx=bf(D), y=bf(D),
                              f=bf(cfg.decoder_ffn_dim), step_cross=bool(step_cross), step_self_min_keys=step_self_min_keys)
 
-    def _gen_prefill(self, st: _GenState, prompt: np.ndarray) -> torch.Tensor:
+    def _gen_prefill(self, st: _GenState, prompt: np.ndarray, also_row: Optional[int] = None, also_target: Optional[int] = None):
         """One teacher-forced pass over ``prompt`` [B, P] at positions 0 .. P - 1 (``ssak_dec_attention_fwd``, causal), its
-        self-attention k|v into the cache -> the logits [B, Vp] fp32 of the LAST prompt row only."""
+        self-attention k|v into the cache -> the logits [B, Vp] fp32 of the LAST prompt row only.  With ``also_row`` (a prompt
+        position) that row is projected as well, first, through the same workspace, and the return value is (logits of the last
+        row, log-softmax of column ``also_target`` on row ``also_row`` [B] fp32 on the device: ``ssak_token_logprobs``)."""
         B, P = prompt.shape
         if st.t != 0 or P > st.cap:
             raise ValueError(f"prefill of {P} tokens into a cache of {st.cap} rows with {st.t} in use")
         x = self._decoder_hidden(st.enc, prompt, st.enc_lens_host, 0, cross_kv=st.cross_kv, self_cache=st.self_kv)
         st.t = P
         with torch.cuda.device(self.device):
-            return self._project(x.view(B, P, st.D)[:, P - 1].contiguous(), B)
+            if also_row is None:
+                return self._project(x.view(B, P, st.D)[:, P - 1].contiguous(), B)
+            if not 0 <= also_row < P:
+                raise ValueError(f"also_row {also_row} outside the prompt's {P} positions")
+            side = self._project(x.view(B, P, st.D)[:, also_row].contiguous(), B)
+            lp = hip.token_logprobs(side, self.config.vocab_size, np.full(B, int(also_target), dtype=np.int32))[1]
+            return self._project(x.view(B, P, st.D)[:, P - 1].contiguous(), B), lp
 
     def _gen_attend(self, st: _GenState, kind: str, q, kv, n_keys: int):
         """ctx [B, D] of the one new row: ``kv`` [B, rows, 2 D] is a layer's cache (``kind`` "self": the first ``n_keys`` rows
@@ -579,15 +599,17 @@ class WhisperSeq2Seq:
         m[ids] = 1
         return torch.from_numpy(m).to(self.device)
 
-    def default_prompt(self, B: int, language=None, task: str = "transcribe") -> np.ndarray:
+    def default_prompt(self, B: int, language=None, task: str = "transcribe", timestamps: bool = False) -> np.ndarray:
         """``[<|startoftranscript|>, language, task, <|notimestamps|>]`` per utterance, [B, 4] (``language``: one code or B codes;
-        a model without language tokens gets ``[<|startoftranscript|>, <|notimestamps|>]``)."""
+        a model without language tokens gets ``[<|startoftranscript|>, <|notimestamps|>]``).  ``timestamps``: the same without
+        the closing ``<|notimestamps|>``, [B, 3] (or [B, 1])."""
         cfg = self.config
         if cfg.no_timestamps_token_id is None:
             raise ValueError("the model folder names no no_timestamps_token_id (generation_config.json): pass prompt=")
+        tail = [] if timestamps else [cfg.no_timestamps_token_id]
         codes = cfg.lang_to_id or {}
         if not codes:
-            return np.tile(np.array([[cfg.decoder_start_token_id, cfg.no_timestamps_token_id]], dtype=np.int64), (B, 1))
+            return np.tile(np.array([[cfg.decoder_start_token_id] + tail], dtype=np.int64), (B, 1))
         if language is None:
             raise ValueError("default_prompt needs the language (one code or one per utterance); generate() detects it when none is given")
         langs = [language] * B if isinstance(language, str) else list(language)
@@ -598,11 +620,12 @@ class WhisperSeq2Seq:
                 raise ValueError(f"language {c!r}: the model knows {sorted(codes)}")
         if not cfg.task_to_id or task not in cfg.task_to_id:
             raise ValueError(f"task {task!r}: the model folder's task_to_id is {cfg.task_to_id}")
-        return np.array([[cfg.decoder_start_token_id, codes[c], cfg.task_to_id[task], cfg.no_timestamps_token_id] for c in langs], dtype=np.int64)
+        return np.array([[cfg.decoder_start_token_id, codes[c], cfg.task_to_id[task]] + tail for c in langs], dtype=np.int64)
 
     def generate(self, enc_or_audio, prompt=None, language=None, task: str = "transcribe", max_new_tokens: Optional[int] = None, enc_lens=None,
-                 suppress_tokens=None, begin_suppress_tokens=None, eos_token_id: Optional[int] = None, poll_every: int = 8) -> GenerateResult:
-        """Greedy transcription (temperature 0, no beam, no timestamps) of a batch in lock step -> :class:`GenerateResult`.
+                 suppress_tokens=None, begin_suppress_tokens=None, eos_token_id: Optional[int] = None, poll_every: int = 8,
+                 timestamps: bool = False) -> GenerateResult:
+        """Greedy transcription (temperature 0, no beam) of a batch in lock step -> :class:`GenerateResult`.
 
         ``prompt`` [B, P] or [P] ids (one P for the batch); by default ``[<|startoftranscript|>, language, task,
         <|notimestamps|>]``, where ``language = None`` runs :meth:`detect_language`'s pass first (on this call's cross k|v buffer) and gives each
@@ -615,8 +638,17 @@ class WhisperSeq2Seq:
         bf16 buffer -- 1.77 GB at whisper-small with B = 32 -- next to the [layers, B, P + max_new_tokens, 2 D] cache.
         The host reads nothing per token: every ``poll_every`` steps it reads the count of unfinished utterances through a pinned
         word and stops at 0 (``poll_every = 0``: never, the loop runs ``max_new_tokens`` steps); tokens and log-probabilities
-        are copied once at the end."""
+        are copied once at the end.
+
+        ``timestamps=True``: whisper's timestamp rules (``ssak_dec_timestamp_step``; the first timestamp at most
+        ``max_initial_timestamp_index``), the default prompt without ``<|notimestamps|>``, by default at most
+        ``min(max_target_positions // 2, max_target_positions - P)`` tokens (whisper's ``sample_len``), and ``no_speech_prob``
+        in the result.  The default leaves the call as it was."""
         cfg = self.config
+        timestamps = bool(timestamps)
+        if timestamps and cfg.no_timestamps_token_id is None:
+            raise ValueError("timestamps=True: the model folder names no no_timestamps_token_id (generation_config.json), the timestamp ids are "
+                             "those above it")
         enc = self._as_enc(enc_or_audio)
         B = enc.shape[0]
         V, maxp = cfg.vocab_size, cfg.max_target_positions
@@ -630,16 +662,16 @@ class WhisperSeq2Seq:
         if detect:
             if not cfg.task_to_id or task not in cfg.task_to_id or cfg.no_timestamps_token_id is None:
                 raise ValueError(f"task {task!r} / no_timestamps_token_id: the model folder's generation_config.json names neither: pass prompt=")
-            P = 4
+            P = 3 if timestamps else 4
         else:
             if prompt is None:
-                prompt = self.default_prompt(B, language, task)
+                prompt = self.default_prompt(B, language, task, timestamps)
             prompt = np.asarray(prompt.cpu() if torch.is_tensor(prompt) else prompt, dtype=np.int64)
             prompt = np.ascontiguousarray(np.broadcast_to(prompt, (B, prompt.shape[-1])) if prompt.ndim == 1 else prompt)
             if prompt.ndim != 2 or prompt.shape[0] != B or prompt.shape[1] < 1:
                 raise ValueError(f"prompt [B, P] or [P] for {B} utterances, got shape {prompt.shape}")
             P = prompt.shape[1]
-        n_max = maxp - P if max_new_tokens is None else int(max_new_tokens)
+        n_max = (min(maxp // 2, maxp - P) if timestamps else maxp - P) if max_new_tokens is None else int(max_new_tokens)
         if n_max < 1 or P + n_max > maxp:
             raise ValueError(f"prompt of {P} + max_new_tokens {n_max} tokens: the decoder has max_target_positions = {maxp} positions")
         if poll_every < 0:
@@ -648,8 +680,21 @@ class WhisperSeq2Seq:
         bsup = self._token_mask(cfg.begin_suppress_tokens if begin_suppress_tokens is None else begin_suppress_tokens, "begin_suppress_tokens")
         st = self._gen_begin(enc, enc_lens, cap=P + n_max)
         if detect:
-            prompt = self.default_prompt(B, self._detect_language(enc, st.enc_lens_host, cross_kv=st.cross_kv)[0], task)
-        logits = self._gen_prefill(st, prompt)
+            prompt = self.default_prompt(B, self._detect_language(enc, st.enc_lens_host, cross_kv=st.cross_kv)[0], task, timestamps)
+        no_speech = None
+        if timestamps:
+            ts_begin = int(cfg.no_timestamps_token_id) + 1
+            max_initial = -1 if cfg.max_initial_timestamp_index is None else int(cfg.max_initial_timestamp_index)
+            ns_id = int(cfg.no_timestamps_token_id) - 1 if cfg.no_speech_token_id is None else int(cfg.no_speech_token_id)
+            sot_rows = [int(np.argmax(r == cfg.decoder_start_token_id)) if (r == cfg.decoder_start_token_id).any() else -1 for r in prompt]
+            if min(sot_rows) < 0 or len(set(sot_rows)) != 1:
+                raise ValueError("timestamps=True: no_speech_prob is read at the prompt's <|startoftranscript|>, which must sit at one position "
+                                 "in every row")
+            if not 0 <= ns_id < V:
+                raise ValueError(f"no_speech_token_id {ns_id} outside [0, {V})")
+            logits, no_speech = self._gen_prefill(st, prompt, also_row=sot_rows[0], also_target=ns_id)
+        else:
+            logits = self._gen_prefill(st, prompt)
         E, Pz = self._w("embed_tokens.weight"), self._w("embed_positions.weight")
         with torch.cuda.device(self.device):
             tokens = torch.full((B, n_max), pad, dtype=torch.int32, device=self.device)
@@ -659,11 +704,16 @@ class WhisperSeq2Seq:
             word = torch.zeros(1, dtype=torch.int32).pin_memory()
             h_next = torch.empty((B, st.D), dtype=torch.bfloat16, device=self.device)
             steps = 0
+            if timestamps:
+                ts_last = torch.full((B,), -1, dtype=torch.int32, device=self.device)
+                select = lambda **kw: hip.dec_timestamp_step(logits, V, ts_begin=ts_begin, no_timestamps_id=cfg.no_timestamps_token_id,
+                                                             max_initial=max_initial, ts_last=ts_last, **kw)
+            else:
+                select = lambda **kw: hip.dec_greedy_step(logits, V, **kw)
             for i in range(n_max):
                 last = i + 1 == n_max
-                hip.dec_greedy_step(logits, V, finished=finished, n_unfinished=n_unf, tokens=tokens, logprobs=logprobs, t=i, eos_id=eos, pad_id=pad,
-                                    suppress=sup, begin_suppress=bsup, first=i == 0, embed_tokens=E, embed_positions=Pz, next_pos=P + i,
-                                    h_next=None if last else h_next)
+                select(finished=finished, n_unfinished=n_unf, tokens=tokens, logprobs=logprobs, t=i, eos_id=eos, pad_id=pad, suppress=sup,
+                       begin_suppress=bsup, first=i == 0, embed_tokens=E, embed_positions=Pz, next_pos=P + i, h_next=None if last else h_next)
                 steps = i + 1
                 if last:
                     break
@@ -675,6 +725,8 @@ class WhisperSeq2Seq:
                 logits = self._gen_step(st, h_next)
             tok = tokens[:, :steps].cpu().numpy()
             lp = logprobs[:, :steps].double().cpu().numpy()
+            if no_speech is not None:
+                no_speech = np.exp(no_speech.double().cpu().numpy())
         lens = np.array([int(np.argmax(r == eos)) + 1 if (r == eos).any() else steps for r in tok], dtype=np.int64)
         n = int(lens.max())
         tok, lp = tok[:, :n].copy(), lp[:, :n].copy()
@@ -683,4 +735,11 @@ class WhisperSeq2Seq:
             lp[b, lens[b]:] = 0.0
         s = lp.sum(-1)
         return GenerateResult(tokens=[tok[b, :lens[b]].tolist() for b in range(B)], lens=lens, token_array=tok, logprobs=lp, sum_logprob=s,
-                              avg_logprob=s / (lens + 1), steps=steps)
+                              avg_logprob=s / (lens + 1), steps=steps, no_speech_prob=no_speech)
+
+    def transcribe(self, waveforms, language=None, task: str = "transcribe", no_speech_threshold: Optional[float] = 0.6,
+                   logprob_threshold: Optional[float] = -1.0, batch_size: int = 8, **kw):
+        """Long-form transcription with timestamps: :func:`ssak_amd.whisper_transcribe.transcribe`."""
+        from .whisper_transcribe import transcribe
+        return transcribe(self, waveforms, language=language, task=task, no_speech_threshold=no_speech_threshold,
+                          logprob_threshold=logprob_threshold, batch_size=batch_size, **kw)
