@@ -116,7 +116,8 @@ def clear_wav_cache() -> None:
 
 def segment_range(info: WavInfo, start: Optional[float], end: Optional[float]) -> Tuple[int, int]:
     """(file offset, frames) of the segment: offset = int(start * sr) frames in, int((end - start) * sr) frames long, clipped to the
-    file (audio.py:85-92)."""
+    file (audio.py:85-92).  One deliberate difference: a segment shorter than one sample, int((end - start) * sr) == 0, is 0 frames
+    here, while the reference passes that 0 to its reader as nframes (audio.py:88-92), where it means "to the end of the file"."""
     n, sr = info.frames, info.sample_rate
     s0 = min(n, int(float(start) * sr)) if start else 0
     cnt = min(n - s0, int((float(end) - float(start or 0)) * sr)) if end else n - s0
