@@ -777,6 +777,55 @@ int ssak_dec_timestamp_step(const float* logits, long ldv, int B, int V, const u
                             int ts_begin, int no_timestamps_id, int max_initial, const void* embed_tokens, const void* embed_positions, int D,
                             int max_positions, int next_pos, int eos_id, int pad_id, uint8_t* finished, int32_t* n_unfinished,
                             int32_t* tokens, float* logprobs, long ldt, int t, int32_t* ts_last, void* h_next, void* stream);
+/* ---- Whisper beam search (ABI 630): nb hypotheses per audio, R = B * nb rows, K = nb + 1 candidates per row ----------------
+ * What whisper/decoding.py BeamSearchDecoder does per step, on the device, with the conventions of ABI 610 / 620: no host mirrors,
+ * nothing read back, fp32 sums in a fixed order, integer atomics only; a refusal returns SSAK_ERR_INVALID and launches nothing.
+ * 1 <= nb <= 8, B * nb <= 65535.  The rules are stated once in DESIGN.md "Whisper beam search".
+ *
+ * ssak_dec_beam_topk.  Per row of logits [R, ldv] fp32: the row is filtered exactly as ssak_dec_timestamp_step filters it
+ * (timestamps != 0: suppress masks, `first`, ts_begin, no_timestamps_id, max_initial, the row's own history tokens[row * ldt + 0 ..
+ * t - 1] and ts_last[row], the mass rule) or as ssak_dec_greedy_step does (timestamps == 0: the masks alone; tokens, ts_last and the
+ * timestamp arguments are not read); logprob = the log-softmax of the processed row.  cand_token [R, K] int32 / cand_logprob [R, K]
+ * fp32 receive the K largest log-probs, highest first, a tie to the lowest column; slots beyond the allowed columns hold -1 /
+ * -inf.  When the mass rule fires every candidate is a timestamp.  done [B] uint8: the rows of a done audio are skipped, their
+ * slots left as they are.  K must be nb + 1.
+ *
+ * ssak_dec_beam_select.  One step of the search per audio on cand_* and sum_logprob [B, nb] fp32 (a call starts with [0, -inf, ...]
+ * per audio).  A candidate (beam j, rank r) exists when sum_logprob[j] > -inf and its token is >= 0; its score is the fp32 sum
+ * sum_logprob[j] + logprob.  The candidates are walked by score descending, then j, then r: an eos_id candidate is newly finished,
+ * any other becomes the next live hypothesis until nb are saved (an eos behind that point is not seen); if the candidates run out
+ * the remaining live slots get sum -inf, token pad_id, source = themselves.  The newly finished are appended in walk order to the
+ * audio's finished store while it holds fewer than nb: fin_tokens / fin_logprobs [B, nb, ldt] = the source's history plus eos_id
+ * and its log-prob at column t, fin_len [B, nb] = t + 1, fin_sum [B, nb] = the score, n_fin [B] the count; done [B] = n_fin == nb.
+ * Written in the same launch: src [R] int32 (GLOBAL row indices), tokens / logprobs [R, ldt] -- the audio's histories permuted by
+ * src IN PLACE (all nb rows of t entries are read before any is written; src may repeat a source; t <= 448) and the new entries
+ * at column t --, the new sums, ts_last [R] (NULL without timestamps: the new token if it is >= ts_begin, else the source's
+ * value), n_unfinished [1] = the audios not done (zeroed by the entry), h_next [R, D] bf16 as ssak_dec_greedy_step forms it (may be
+ * NULL).  An audio that was done on entry emits pad_id with log-prob 0, identity sources, and changes nothing else.
+ *
+ * ssak_dec_kv_reorder.  cache [layers, B * nb, cap, width] bf16 with element strides layer_stride / row_stride / key_stride
+ * (multiples of 8, nested; 16-byte aligned base): for every layer, audio and key in [row_lo, row_hi), row r's bytes become row
+ * src[r]'s, IN PLACE (a thread owns one 16-byte chunk across the audio's nb beams, loads those whose source is another beam, then
+ * stores them).  Beams with src[r] == r move no bytes; bytes outside the key range and in stride gaps are untouched; a source
+ * outside the audio's own beams leaves the beam as it is.  row_lo == row_hi launches nothing.  A range outside [0, cap]:
+ * SSAK_ERR_INVALID.
+ *
+ * ssak_dec_attention_step_grouped.  ssak_dec_attention_step with `group`: query row r reads k / v of utterance r / group and
+ * klens[r / group] (klens has B / group entries), so the nb beams of an audio share its cross k|v buffer.  group must divide B;
+ * group = 1 is ssak_dec_attention_step, which is now this call. */
+int ssak_dec_beam_topk(const float* logits, long ldv, int B, int nb, int V, const uint8_t* suppress, const uint8_t* begin_suppress, int first,
+                       int timestamps, int ts_begin, int no_timestamps_id, int max_initial, int eos_id, const int32_t* tokens, long ldt, int t,
+                       const int32_t* ts_last, const uint8_t* done, int K, int32_t* cand_token, float* cand_logprob, void* stream);
+int ssak_dec_beam_select(const int32_t* cand_token, const float* cand_logprob, int B, int nb, int K, int V, float* sum_logprob, int32_t* src,
+                         int32_t* tokens, float* logprobs, long ldt, int t, int32_t* ts_last, int ts_begin, int32_t* fin_tokens,
+                         float* fin_logprobs, int32_t* fin_len, float* fin_sum, int32_t* n_fin, uint8_t* done, int32_t* n_unfinished,
+                         const void* embed_tokens, const void* embed_positions, int D, int max_positions, int next_pos, int eos_id, int pad_id,
+                         void* h_next, void* stream);
+int ssak_dec_kv_reorder(void* cache, const int32_t* src, int layers, int B, int nb, int cap, int width, long layer_stride, long row_stride,
+                        long key_stride, int row_lo, int row_hi, void* stream);
+int ssak_dec_attention_step_grouped(const void* q, long ldq, const void* k, long ldk, long k_batch_stride, const void* v, long ldv,
+                                    long v_batch_stride, int n_keys, const int32_t* klens, int B, int nh, int head_dim, int n_split, int group,
+                                    void* workspace, size_t workspace_bytes, void* ctx, void* stream);
 /* r = res + y (either may be NULL) -> r_out (may be NULL), out = LayerNorm(r) * gamma + beta (may be NULL) on [M, C] rows of
  * dtype 0 = bf16 / 1 = fp32: the row kernel of the encoder layers without dropout sites or saved statistics.  C a multiple of
  * 8, <= 1536. */

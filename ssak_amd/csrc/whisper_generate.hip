@@ -13,7 +13,9 @@
 // into the second product and the row sum is the sum of the same unrounded P.  The 32 (wave, group) partials of a workgroup
 // meet in LDS in (wave, group) order; with n_split > 1 the workgroup's (max, sum, O[64]) go to the workspace in fp32 and
 // dec_attn_combine_kernel merges the splits in split order.  A partial that saw no key has maximum -inf and sum 0: its factor is
-// taken as 0, never exp2(-inf - -inf).  No float atomics, no arrival order: two runs give the same bits.
+// taken as 0, never exp2(-inf - -inf).  No float atomics, no arrival order: two runs give the same bits.  With `group` > 1 (ABI 630,
+// ssak_dec_attention_step_grouped) query row b reads the keys and klens of utterance b / group: the beams of an audio share its
+// cross k|v buffer.
 //
 // dec_greedy_kernel.  One workgroup per row, the two-pass shape of token_logprobs_kernel with the suppress masks applied as the
 // columns are read.
@@ -29,6 +31,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "whisper_step.h"
 
 namespace {
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -54,6 +57,7 @@ struct AsParams {
   float* ws_o;  // [B * nh * n_split, 64]
   long ldq, ldk, ldv, k_batch_stride, v_batch_stride;
   int n_keys, nh, n_split, chunk;
+  int group;  // query row b reads the keys of utterance b / group (the beams of an audio share its cross k|v)
 };
 
 // the sum over the 8 lanes of a key (lanes 8 g .. 8 g + 7): quad swaps, then the mirror of the 8-lane half row
@@ -70,15 +74,16 @@ __global__ __launch_bounds__(AS_THREADS) void dec_attn_step_kernel(const AsParam
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 3, c = lane & 7;
   const int s = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   // klens is validated once by the caller that uploaded it; the clamp keeps any value inside the cache
-  const int klen = p.klens ? min(max(p.klens[b], 1), p.n_keys) : p.n_keys;
+  const int bk = b / p.group;  // the utterance whose keys this query row reads
+  const int klen = p.klens ? min(max(p.klens[bk], 1), p.n_keys) : p.n_keys;
   const int k0 = s * p.chunk, k1 = min(min(k0 + p.chunk, p.n_keys), klen);  // this workgroup's visible keys: [k0, k1), maybe empty
 
   float qf[8];
   chunk_to_f(ld8<bf16>(p.q + (long)b * p.ldq + h * AS_HD + 8 * c), qf);
 #pragma unroll
   for (int e = 0; e < 8; ++e) qf[e] *= 0.125f;  // (exact)
-  const bf16* const kb = p.k + (long)b * p.k_batch_stride + h * AS_HD + 8 * c;
-  const bf16* const vb = p.v + (long)b * p.v_batch_stride + h * AS_HD + 8 * c;
+  const bf16* const kb = p.k + (long)bk * p.k_batch_stride + h * AS_HD + 8 * c;
+  const bf16* const vb = p.v + (long)bk * p.v_batch_stride + h * AS_HD + 8 * c;
 
   float m = -INFINITY, l = 0.f, o[8];  // log2-domain running maximum, row sum and O of this lane group's keys
 #pragma unroll
@@ -190,7 +195,7 @@ void choose_split(int bh, int n_keys, int n_split, int* ns, int* chunk) {
 }
 
 // ---- ssak_dec_greedy_step ----------------------------------------------------------------------------------------------------
-constexpr int GS_THREADS = 256;
+// (GS_THREADS, the timestamp rules and block_argmax: whisper_step.h, shared with whisper_beam.hip)
 
 struct GsParams {
   const float* logits;
@@ -293,17 +298,7 @@ __global__ __launch_bounds__(GS_THREADS) void dec_greedy_kernel(const GsParams p
     p.finished[row] = now_finished ? 1 : 0;
     if (!now_finished) atomicAdd(p.n_unfinished, 1);  // (an integer count on the word the entry zeroed: order-free)
   }
-  if (p.h_next) {
-    const int id = min(max(token, 0), p.V - 1);
-    for (int ch = tid; ch < (p.D >> 3); ch += GS_THREADS) {
-      float e[8], q[8];
-      chunk_to_f(ld8<bf16>(p.embed_tokens + (long)id * p.D + ch * 8), e);
-      chunk_to_f(ld8<bf16>(p.embed_positions + (long)p.next_pos * p.D + ch * 8), q);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) e[k] += q[k];
-      st8<bf16>(p.h_next + (long)row * p.D + ch * 8, f_to_chunk8<bf16>(e));
-    }
-  }
+  if (p.h_next) form_h_next(p.h_next + (long)row * p.D, p.embed_tokens, p.embed_positions, token, p.V, p.D, p.next_pos);
 }
 
 // ---- ssak_dec_timestamp_step -------------------------------------------------------------------------------------------------
@@ -312,34 +307,6 @@ struct TsParams {
   int32_t* ts_last;
   int ts_begin, no_timestamps_id, max_initial;
 };
-
-// (value, lowest column) of the maximum over the workgroup: lanes, then waves; every thread returns the same pair
-__device__ __forceinline__ void block_argmax(float& best, int32_t& bi, float* red, int32_t* ired) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const float ov = __shfl_xor(best, o);
-    const int32_t oi = __shfl_xor(bi, o);
-    if (ov > best || (ov == best && oi < bi)) {
-      best = ov;
-      bi = oi;
-    }
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6] = best;
-    ired[threadIdx.x >> 6] = bi;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int ww = 0; ww < GS_THREADS / 64; ++ww) {
-    const float ov = red[ww];
-    const int32_t oi = ired[ww];
-    if (ov > best || (ov == best && oi < bi)) {
-      best = ov;
-      bi = oi;
-    }
-  }
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(GS_THREADS) void dec_timestamp_kernel(const TsParams q) {
@@ -357,18 +324,10 @@ __global__ __launch_bounds__(GS_THREADS) void dec_timestamp_kernel(const TsParam
   if (!was_finished) {  // (uniform over the workgroup)
     const int V = p.V, n = p.t, tsb = q.ts_begin;
     const int32_t* const hist = p.tokens + (long)row * p.ldt;
-    const bool last = n >= 1 && hist[n - 1] >= tsb;
-    const bool pen = n < 2 || hist[n - 2] >= tsb;
     const int ts_prev = n == 0 ? -1 : q.ts_last[row];  // (every thread reads it before thread 0 writes it, behind the barriers below)
     ts_new = ts_prev;
-    // the rules as two intervals: text columns [text_lo, tsb), timestamp columns [ts_lo, ts_hi]
-    const int text_lo = n == 0 ? tsb : (last && !pen ? p.eos_id : 0);
-    int ts_lo = tsb, ts_hi = V - 1;
-    if (ts_prev >= 0) ts_lo = max(ts_lo, last && !pen ? ts_prev : ts_prev + 1);
-    if (n == 0 && q.max_initial >= 0) ts_hi = min((long)ts_hi, (long)tsb + q.max_initial);
-    if (last && pen) ts_hi = -1;
-    const int nots = q.no_timestamps_id;
-    const auto allowed = [&](int c) { return c != nots && ((c >= text_lo && c < tsb) || (c >= ts_lo && c <= ts_hi)); };
+    const TsRules rules = ts_rules(hist, n, ts_prev, V, tsb, p.eos_id, q.no_timestamps_id, q.max_initial);
+    const auto allowed = [&](int c) { return rules.allowed(c); };
 
     const int n4 = VEC ? (V & ~3) : 0;
     float mt = -INFINITY, ms = -INFINITY;  // the text maximum, the timestamp maximum
@@ -426,7 +385,7 @@ __global__ __launch_bounds__(GS_THREADS) void dec_timestamp_kernel(const TsParam
       st = block_sum(st, red);
       ss = block_sum(ss, red);
       // the timestamps' mass against the likeliest text token: log S_ts - log S > m_text - M - log S
-      if (ss > 0.f && logf(ss) > mt - M) {
+      if (ts_mass_wins(ss, mt, M)) {
         token = is;
         logprob = (ms - M) - logf(ss);
       } else {
@@ -444,17 +403,7 @@ __global__ __launch_bounds__(GS_THREADS) void dec_timestamp_kernel(const TsParam
     if (!was_finished) q.ts_last[row] = ts_new;
     if (!now_finished) atomicAdd(p.n_unfinished, 1);  // (an integer count on the word the entry zeroed: order-free)
   }
-  if (p.h_next) {
-    const int id = min(max(token, 0), p.V - 1);
-    for (int ch = tid; ch < (p.D >> 3); ch += GS_THREADS) {
-      float e[8], r[8];
-      chunk_to_f(ld8<bf16>(p.embed_tokens + (long)id * p.D + ch * 8), e);
-      chunk_to_f(ld8<bf16>(p.embed_positions + (long)p.next_pos * p.D + ch * 8), r);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) e[k] += r[k];
-      st8<bf16>(p.h_next + (long)row * p.D + ch * 8, f_to_chunk8<bf16>(e));
-    }
-  }
+  if (p.h_next) form_h_next(p.h_next + (long)row * p.D, p.embed_tokens, p.embed_positions, token, p.V, p.D, p.next_pos);
 }
 }  // namespace
 
@@ -464,12 +413,13 @@ extern "C" size_t ssak_dec_attention_step_workspace_bytes(int B, int nh, int n_s
   return (size_t)B * nh * ns * (AS_HD + 2) * sizeof(float);
 }
 
-extern "C" int ssak_dec_attention_step(const void* q, long ldq, const void* k, long ldk, long k_batch_stride, const void* v, long ldv,
-                                       long v_batch_stride, int n_keys, const int32_t* klens, int B, int nh, int head_dim, int n_split,
-                                       void* workspace, size_t workspace_bytes, void* ctx, void* stream) {
+extern "C" int ssak_dec_attention_step_grouped(const void* q, long ldq, const void* k, long ldk, long k_batch_stride, const void* v, long ldv,
+                                               long v_batch_stride, int n_keys, const int32_t* klens, int B, int nh, int head_dim, int n_split,
+                                               int group, void* workspace, size_t workspace_bytes, void* ctx, void* stream) {
   SSAK_REQUIRE(q && k && v && ctx, "dec_attention_step: null pointer");
   SSAK_REQUIRE(head_dim == AS_HD, "dec_attention_step: head_dim=%d; the supported head dimension is %d", head_dim, AS_HD);
   SSAK_REQUIRE(B > 0 && B <= 65535 && nh > 0 && nh <= 65535, "dec_attention_step: bad shape B=%d nh=%d", B, nh);
+  SSAK_REQUIRE(group >= 1 && B % group == 0, "dec_attention_step: group=%d does not divide the %d query rows", group, B);
   SSAK_REQUIRE(n_keys >= 1, "dec_attention_step: n_keys=%d, at least one key is needed", n_keys);
   SSAK_REQUIRE(n_split >= 0 && n_split <= AS_MAX_SPLIT, "dec_attention_step: n_split=%d outside [0, %d] (0 = the library chooses)", n_split,
                AS_MAX_SPLIT);
@@ -496,7 +446,7 @@ extern "C" int ssak_dec_attention_step(const void* q, long ldq, const void* k, l
     p.ws_l = p.ws_m + slots;
   }
   p.ldq = ldq, p.ldk = ldk, p.ldv = ldv, p.k_batch_stride = k_batch_stride, p.v_batch_stride = v_batch_stride;
-  p.n_keys = n_keys, p.nh = nh, p.n_split = ns, p.chunk = chunk;
+  p.n_keys = n_keys, p.nh = nh, p.n_split = ns, p.chunk = chunk, p.group = group;
   const hipStream_t st = (hipStream_t)stream;
   dec_attn_step_kernel<<<dim3(ns, nh, B), AS_THREADS, 0, st>>>(p);
   SSAK_LAUNCH_CHECK();
@@ -505,6 +455,13 @@ extern "C" int ssak_dec_attention_step(const void* q, long ldq, const void* k, l
     SSAK_LAUNCH_CHECK();
   }
   return SSAK_OK;
+}
+
+extern "C" int ssak_dec_attention_step(const void* q, long ldq, const void* k, long ldk, long k_batch_stride, const void* v, long ldv,
+                                       long v_batch_stride, int n_keys, const int32_t* klens, int B, int nh, int head_dim, int n_split,
+                                       void* workspace, size_t workspace_bytes, void* ctx, void* stream) {
+  return ssak_dec_attention_step_grouped(q, ldq, k, ldk, k_batch_stride, v, ldv, v_batch_stride, n_keys, klens, B, nh, head_dim, n_split, 1,
+                                         workspace, workspace_bytes, ctx, stream);
 }
 
 namespace {

@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 620  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 630  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -184,6 +184,12 @@ def _load():
         "ssak_dec_greedy_step": (i32, [vp, C.c_long, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_long, i32, vp, vp]),
         "ssak_dec_timestamp_step": (i32, [vp, C.c_long, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_long,
                                           i32, vp, vp, vp]),
+        "ssak_dec_beam_topk": (i32, [vp, C.c_long, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, C.c_long, i32, vp, vp, i32, vp, vp, vp]),
+        "ssak_dec_beam_select": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, C.c_long, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32,
+                                       i32, i32, i32, i32, vp, vp]),
+        "ssak_dec_kv_reorder": (i32, [vp, vp, i32, i32, i32, i32, i32, C.c_long, C.c_long, C.c_long, i32, i32, vp]),
+        "ssak_dec_attention_step_grouped": (i32, [vp, C.c_long, vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, i32, vp, i32, i32, i32, i32, i32, vp,
+                                                  sz, vp, vp]),
         "ssak_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]),
         "ssak_debug_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, C.c_long, i32, vp, C.POINTER(f32), vp]),
         "ssak_debug_attention_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, i32, i32, i32, vp, vp]),
@@ -825,6 +831,99 @@ def dec_timestamp_step(logits, V: int, *, finished, n_unfinished, tokens, logpro
                                       int(ts_begin), int(no_timestamps_id), int(max_initial), ptr(embed_tokens), ptr(embed_positions), D,
                                       max_pos, int(next_pos), int(eos_id), int(pad_id), ptr(finished), ptr(n_unfinished), ptr(tokens),
                                       ptr(logprobs), tokens.shape[1], int(t), ptr(ts_last), ptr(h_next), stream()))
+
+
+# ------------------------------------------------------------------ Whisper beam search (ABI 630): nb hypotheses per audio, R = B * nb rows
+def dec_attention_step_grouped(q, k, v, n_keys: int, nh: int, group: int, *, klens=None, n_split: int = 0, workspace=None,
+                               head_dim: int = DEC_HEAD_DIM, ctx=None):
+    """``ssak_dec_attention_step_grouped``: :func:`dec_attention_step` where query row ``r`` of q [R, ldq] reads k / v [R / group,
+    capacity, ld] of utterance ``r // group`` and ``klens[r // group]``: the beams of an audio share one cross k|v buffer."""
+    assert q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 2 and q.stride(1) == 1
+    R, group = q.shape[0], int(group)
+    for t in (k, v):
+        assert t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 3 and t.stride(2) == 1
+        assert group < 1 or R % group or t.shape[0] == R // group  # (a group that does not divide the rows is the library's refusal)
+    assert klens is None or (klens.is_cuda and klens.dtype == torch.int32 and klens.is_contiguous() and klens.numel() * max(group, 1) >= R)
+    if workspace is None:
+        workspace = dec_attention_step_workspace(R, nh, n_split, q.device)
+    ctx = torch.empty((R, nh * head_dim), dtype=torch.bfloat16, device=q.device) if ctx is None else ctx
+    check(lib.ssak_dec_attention_step_grouped(ptr(q), q.stride(0), ptr(k), k.stride(1), k.stride(0), ptr(v), v.stride(1), v.stride(0), int(n_keys),
+                                              ptr(klens), R, int(nh), int(head_dim), int(n_split), group, ptr(workspace), workspace.numel() * 4,
+                                              ptr(ctx), stream()))
+    return ctx
+
+
+def dec_beam_topk(logits, V: int, nb: int, *, done, cand_token, cand_logprob, eos_id: int, t: int = 0, suppress=None, begin_suppress=None,
+                  first: bool = False, timestamps: bool = False, ts_begin: int = 0, no_timestamps_id: int = 0, max_initial: int = -1, tokens=None,
+                  ts_last=None):
+    """``ssak_dec_beam_topk`` on logits [B * nb, ldv] fp32: per row the ``K = nb + 1`` largest log-probs of the processed row into
+    ``cand_token`` int32 / ``cand_logprob`` fp32 [B * nb, K], highest first, a tie to the lowest column, -1 / -inf in unused slots.
+    ``timestamps``: the rules of :func:`dec_timestamp_step` on ``tokens[:, :t]`` and ``ts_last`` [B * nb]; otherwise
+    :func:`dec_greedy_step`'s.  ``done``: uint8 [B]; a done audio's rows are skipped."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    R, nb = logits.shape[0], int(nb)
+    B = R // max(nb, 1)
+    assert nb < 1 or B * nb == R
+    assert done.dtype == torch.uint8 and done.numel() == B and done.is_contiguous()
+    assert cand_token.dtype == torch.int32 and cand_logprob.dtype == torch.float32 and cand_token.shape == cand_logprob.shape
+    assert cand_token.dim() == 2 and cand_token.shape[0] == R and cand_token.is_contiguous() and cand_logprob.is_contiguous()
+    for m in (suppress, begin_suppress):
+        assert m is None or (m.is_cuda and m.dtype == torch.uint8 and m.numel() == V and m.is_contiguous())
+    ldt = 0
+    if tokens is not None:
+        assert tokens.dtype == torch.int32 and tokens.is_contiguous() and tokens.shape[0] == R
+        ldt = tokens.shape[1]
+    assert ts_last is None or (ts_last.dtype == torch.int32 and ts_last.numel() == R and ts_last.is_contiguous())
+    check(lib.ssak_dec_beam_topk(ptr(logits), logits.stride(0), B, nb, int(V), ptr(suppress), ptr(begin_suppress), int(bool(first)),
+                                 int(bool(timestamps)), int(ts_begin), int(no_timestamps_id), int(max_initial), int(eos_id), ptr(tokens), ldt, int(t),
+                                 ptr(ts_last), ptr(done), cand_token.shape[1], ptr(cand_token), ptr(cand_logprob), stream()))
+
+
+def dec_beam_select(cand_token, cand_logprob, nb: int, V: int, *, sum_logprob, src, tokens, logprobs, t: int, fin_tokens, fin_logprobs, fin_len,
+                    fin_sum, n_fin, done, n_unfinished, eos_id: int, pad_id: int, ts_last=None, ts_begin: int = 0, embed_tokens=None,
+                    embed_positions=None, next_pos: int = 0, h_next=None):
+    """``ssak_dec_beam_select``: one step of the beam search per audio on the candidates of :func:`dec_beam_topk` (the header states
+    the rules).  Read and written on the device: ``sum_logprob`` fp32 [B, nb], ``tokens`` int32 / ``logprobs`` fp32 [B * nb, ldt]
+    (permuted in place, column ``t`` written), ``ts_last`` int32 [B * nb] or None, the finished store ``fin_tokens`` / ``fin_logprobs``
+    [B, nb, ldt], ``fin_len`` int32 / ``fin_sum`` fp32 [B, nb], ``n_fin`` int32 [B], ``done`` uint8 [B]; written: ``src`` int32 [B * nb],
+    ``n_unfinished`` int32 [1], ``h_next`` [B * nb, D] bf16 (or None)."""
+    R, nb = cand_token.shape[0], int(nb)
+    B = R // max(nb, 1)
+    assert nb < 1 or B * nb == R
+    assert cand_token.dtype == torch.int32 and cand_logprob.dtype == torch.float32 and cand_token.shape == cand_logprob.shape
+    assert cand_token.is_contiguous() and cand_logprob.is_contiguous()
+    assert tokens.dtype == torch.int32 and logprobs.dtype == torch.float32 and tokens.shape == logprobs.shape and tokens.shape[0] == R
+    assert tokens.is_contiguous() and logprobs.is_contiguous()
+    ldt = tokens.shape[1]
+    assert sum_logprob.dtype == torch.float32 and sum_logprob.numel() == R and sum_logprob.is_contiguous()
+    assert src.dtype == torch.int32 and src.numel() == R and src.is_contiguous()
+    assert fin_tokens.dtype == torch.int32 and fin_logprobs.dtype == torch.float32 and fin_tokens.numel() == R * ldt == fin_logprobs.numel()
+    assert fin_tokens.is_contiguous() and fin_logprobs.is_contiguous()
+    assert fin_len.dtype == torch.int32 and fin_len.numel() == R and fin_sum.dtype == torch.float32 and fin_sum.numel() == R
+    assert n_fin.dtype == torch.int32 and n_fin.numel() == B and done.dtype == torch.uint8 and done.numel() == B
+    assert n_unfinished.dtype == torch.int32
+    assert ts_last is None or (ts_last.dtype == torch.int32 and ts_last.numel() == R and ts_last.is_contiguous())
+    D = max_pos = 0
+    if h_next is not None:
+        assert embed_tokens.dtype == torch.bfloat16 and embed_tokens.is_contiguous() and embed_positions.is_contiguous()
+        D, max_pos = embed_tokens.shape[1], embed_positions.shape[0]
+        assert h_next.dtype == torch.bfloat16 and h_next.is_contiguous() and tuple(h_next.shape) == (R, D)
+    check(lib.ssak_dec_beam_select(ptr(cand_token), ptr(cand_logprob), B, nb, cand_token.shape[1], int(V), ptr(sum_logprob), ptr(src), ptr(tokens),
+                                   ptr(logprobs), ldt, int(t), ptr(ts_last), int(ts_begin), ptr(fin_tokens), ptr(fin_logprobs), ptr(fin_len),
+                                   ptr(fin_sum), ptr(n_fin), ptr(done), ptr(n_unfinished), ptr(embed_tokens), ptr(embed_positions), D, max_pos,
+                                   int(next_pos), int(eos_id), int(pad_id), ptr(h_next), stream()))
+
+
+def dec_kv_reorder(cache, src, nb: int, row_lo: int, row_hi: int):
+    """``ssak_dec_kv_reorder``: the self-attention cache [layers, B * nb, cap, width] bf16 (any nested strides, the last 1) gathered by
+    ``src`` int32 [B * nb] (global row indices) over the keys ``[row_lo, row_hi)``, in place."""
+    assert cache.is_cuda and cache.dtype == torch.bfloat16 and cache.dim() == 4 and cache.stride(3) == 1
+    assert src.dtype == torch.int32 and src.is_contiguous() and src.numel() == cache.shape[1]
+    nb = int(nb)
+    B = cache.shape[1] // max(nb, 1)
+    assert nb < 1 or B * nb == cache.shape[1]
+    check(lib.ssak_dec_kv_reorder(ptr(cache), ptr(src), cache.shape[0], B, nb, cache.shape[2], cache.shape[3], cache.stride(0), cache.stride(1),
+                                  cache.stride(2), int(row_lo), int(row_hi), stream()))
 
 
 def layernorm_fwd(y, res, gamma, beta, r_out=None, out=None, eps: float = 1e-5):

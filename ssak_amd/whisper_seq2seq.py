@@ -30,11 +30,12 @@ also returns ``no_speech_prob``; :meth:`WhisperSeq2Seq.transcribe` (ssak_amd/whi
 files of any length by the timestamps it predicted, as ``model.transcribe`` does.
 
 Token ids are the contract (no tokenizer is needed, and none is shipped); :meth:`WhisperSeq2Seq.score_text` is a convenience
-that imports ``transformers.WhisperTokenizer`` lazily.  Not built: fallback temperatures and ``compression_ratio_threshold``, beam
-search, ``condition_on_previous_text`` / ``initial_prompt``, word timestamps, a skinny-M GEMM for the token step, hipGraph capture
+that imports ``transformers.WhisperTokenizer`` lazily.  Beam search (``generate(beam_size=N)``, the reference's ``--beam_size`` / ``--accurate``): ``ssak_dec_beam_topk`` /
+``ssak_dec_beam_select`` / ``ssak_dec_kv_reorder`` keep N hypotheses per utterance on the device.  Not built: fallback temperatures,
+sampling, ``best_of``, a beam ``patience`` and ``compression_ratio_threshold``, ``condition_on_previous_text`` / ``initial_prompt``, word timestamps, a skinny-M GEMM for the token step, hipGraph capture
 of the step, training / LoRA, an fp32-exact mode of the decoder.  Timing: tools/bench_whisper_decoder.py,
-tools/bench_whisper_generate.py, tools/bench_whisper_transcribe.py (DESIGN.md "Whisper decoder", "Whisper generation", "Whisper
-long-form transcription").
+tools/bench_whisper_generate.py, tools/bench_whisper_transcribe.py, tools/bench_whisper_beam.py (DESIGN.md "Whisper decoder",
+"Whisper generation", "Whisper long-form transcription", "Whisper beam search").
 """
 from __future__ import annotations
 
@@ -126,7 +127,10 @@ class GenerateResult:
     token's log-softmax under the processed logits, 0 past ``lens``; ``sum_logprob`` [B]; ``avg_logprob`` = sum / (len + 1) as
     :class:`ScoreResult` has it; ``steps``: the token steps the loop ran before it stopped.  ``no_speech_prob`` [B] float64 (only
     with ``timestamps=True``, else None): the softmax probability of the no-speech token on the unprocessed logits of the
-    ``<|startoftranscript|>`` row."""
+    ``<|startoftranscript|>`` row.  ``beams`` (only with ``beam_size``, else None): per utterance the ``beam_size`` candidates
+    ``(tokens, sum_logprob)`` in finalisation order -- the finished sequences in the order they finished, then the live ones by
+    descending sum; the other fields describe the candidate the ranking chose, ``sum_logprob`` being the device's fp32 running sum;
+    ``beam_logprobs``: per utterance and candidate the per-token log-probs (float64 arrays, as long as the candidate's tokens)."""
     tokens: List[List[int]]
     lens: np.ndarray
     token_array: np.ndarray
@@ -135,6 +139,8 @@ class GenerateResult:
     avg_logprob: np.ndarray
     steps: int
     no_speech_prob: Optional[np.ndarray] = None
+    beams: Optional[list] = None
+    beam_logprobs: Optional[list] = None
 
 
 # The shortest self-attention cache on which the token step runs ssak_dec_attention_step; below it, ssak_dec_attention_fwd at
@@ -169,6 +175,61 @@ class _GenState:
     step_cross: bool = True
     step_self_min_keys: Optional[int] = STEP_SELF_MIN_KEYS
     t: int = 0                            # cache rows in use = the next position
+    group: int = 1                        # beam search: decoder rows per utterance (the cache and the step's rows count B * group)
+
+
+@dataclasses.dataclass
+class _BeamState:
+    """The device state of a beam search over ``B`` utterances x ``nb`` hypotheses (R = B * nb rows), advanced by
+    :meth:`WhisperSeq2Seq._beam_step`: what ``ssak_dec_beam_topk`` / ``ssak_dec_beam_select`` read and write (include/ssak_hip.h)."""
+    B: int
+    nb: int
+    P: int                                # prompt length: the reorders cover the cache rows [P, t)
+    eos: int
+    pad: int
+    sup: Optional[torch.Tensor]
+    bsup: Optional[torch.Tensor]
+    ts: Optional[dict]                    # ts_begin, no_timestamps_id, max_initial; None without timestamps
+    tokens: torch.Tensor                  # int32 [R, n_max]
+    logprobs: torch.Tensor                # fp32 [R, n_max]
+    sums: torch.Tensor                    # fp32 [B, nb]: [0, -inf, ...] at the start
+    src: torch.Tensor                     # int32 [R]
+    ts_last: Optional[torch.Tensor]       # int32 [R]
+    cand_token: torch.Tensor              # int32 [R, nb + 1]
+    cand_logprob: torch.Tensor            # fp32 [R, nb + 1]
+    fin_tokens: torch.Tensor              # int32 [B, nb, n_max]
+    fin_logprobs: torch.Tensor
+    fin_len: torch.Tensor                 # int32 [B, nb]
+    fin_sum: torch.Tensor                 # fp32 [B, nb]
+    n_fin: torch.Tensor                   # int32 [B]
+    done: torch.Tensor                    # uint8 [B]
+    n_unf: torch.Tensor                   # int32 [1]
+    h_next: torch.Tensor                  # bf16 [R, D]
+    i: int = 0                            # steps taken = history entries per row
+
+
+def beam_finalize(tokens, sums, fin_tokens, fin_len, fin_sum, n_fin, steps: int, nb: int):
+    """Host half of the beam search for one utterance: the finished sequences in the order they finished, then -- while fewer than
+    ``nb`` -- the live hypotheses by ``list(np.argsort(sums))[::-1]`` (no eos, no eos term in their sum), skipping ``-inf`` ->
+    [(token list, sum, finished?, index)], ``index`` = the sequence's slot in the finished store or the live hypothesis' beam (where
+    its per-token log-probs are).  An utterance with neither (no allowed column at the first step) gets one empty candidate."""
+    out = [([int(x) for x in fin_tokens[k, :fin_len[k]]], float(fin_sum[k]), True, k) for k in range(int(n_fin))]
+    for j in list(np.argsort(sums))[::-1]:
+        if len(out) >= nb:
+            break
+        if sums[j] > -np.inf:
+            out.append(([int(x) for x in tokens[j, :steps]], float(sums[j]), False, int(j)))
+    return out or [([], 0.0, False, -1)]
+
+
+def beam_rank(cands, length_penalty=None) -> int:
+    """whisper's MaximumLikelihoodRanker over the candidates of :func:`beam_finalize`: score = sum / length with length = the
+    tokens before eos (``length_penalty`` a: sum / ((5 + length) / 6) ** a); a length of 0 scores -inf; ``np.argmax`` picks."""
+    scores = []
+    for toks, s, fin, _ in cands:
+        n = len(toks) - 1 if fin else len(toks)
+        scores.append(-np.inf if n == 0 else s / (n if length_penalty is None else ((5 + n) / 6) ** length_penalty))
+    return int(np.argmax(scores))
 
 
 def _decoder_layout(cfg: WhisperSeq2SeqConfig):
@@ -493,12 +554,17 @@ class WhisperSeq2Seq:
 
     # ------------------------------------------------------------------ generation
     def _gen_begin(self, enc: torch.Tensor, enc_lens=None, cap: Optional[int] = None, step_cross: bool = True,
-                   step_self_min_keys: Optional[int] = STEP_SELF_MIN_KEYS) -> _GenState:
+                   step_self_min_keys: Optional[int] = STEP_SELF_MIN_KEYS, group: int = 1) -> _GenState:
         """Everything a call computes once: the twelve cross k|v projections of the encoder output into ONE [layers, B * S, 2 D]
         buffer (1.77 GB at whisper-small, B = 32), the empty self-attention cache, the encoder lengths (validated here, uploaded
-        here, read by the kernels from the device ever after)."""
+        here, read by the kernels from the device ever after).  ``group`` > 1 (beam search): the cache and the step's activation rows
+        count ``B * group``; the cross buffer stays at B utterances and the step reads it through ``ssak_dec_attention_step_grouped``."""
         cfg = self.config
         B, S, D = enc.shape
+        group = int(group)
+        if group > 1 and not step_cross:
+            raise ValueError("group > 1: the beams share the cross k|v buffer through the step kernel only (step_cross)")
+        R = B * group
         cap = cfg.max_target_positions if cap is None else int(cap)
         lens_host = lens_dev = None
         if enc_lens is not None:
@@ -513,11 +579,11 @@ class WhisperSeq2Seq:
             for l in range(nl):
                 p = f"layers.{l}.encoder_attn.k_proj."
                 hip.gemm(enc2, self._w(p + "weight", 2), cross_kv[l], B * S, 2 * D, D, lda=D, ldb=D, ldc=2 * D, bias=self._f(p + "bias", 2))
-            bf = lambda n: torch.empty((B, n), dtype=torch.bfloat16, device=self.device)
+            bf = lambda n: torch.empty((R, n), dtype=torch.bfloat16, device=self.device)
             return _GenState(B=B, S=S, D=D, cap=cap, enc=enc, enc_lens=lens_dev, enc_lens_host=lens_host, cross_kv=cross_kv,
-                             self_kv=torch.zeros((nl, B, cap, 2 * D), dtype=torch.bfloat16, device=self.device),
-                             ws=hip.dec_attention_step_workspace(B, nh, 0, self.device), h=bf(D), h2=bf(D), x=bf(D), q=bf(D), ctx=bf(D), y=bf(D),
-                             f=bf(cfg.decoder_ffn_dim), step_cross=bool(step_cross), step_self_min_keys=step_self_min_keys)
+                             self_kv=torch.zeros((nl, R, cap, 2 * D), dtype=torch.bfloat16, device=self.device),
+                             ws=hip.dec_attention_step_workspace(R, nh, 0, self.device), h=bf(D), h2=bf(D), x=bf(D), q=bf(D), ctx=bf(D), y=bf(D),
+                             f=bf(cfg.decoder_ffn_dim), step_cross=bool(step_cross), step_self_min_keys=step_self_min_keys, group=group)
 
     def _gen_prefill(self, st: _GenState, prompt: np.ndarray, also_row: Optional[int] = None, also_target: Optional[int] = None):
         """One teacher-forced pass over ``prompt`` [B, P] at positions 0 .. P - 1 (``ssak_dec_attention_fwd``, causal), its
@@ -527,7 +593,13 @@ class WhisperSeq2Seq:
         B, P = prompt.shape
         if st.t != 0 or P > st.cap:
             raise ValueError(f"prefill of {P} tokens into a cache of {st.cap} rows with {st.t} in use")
-        x = self._decoder_hidden(st.enc, prompt, st.enc_lens_host, 0, cross_kv=st.cross_kv, self_cache=st.self_kv)
+        # (beam search: the prompt runs once per utterance, its k|v into the cache rows of beam 0, then copied once to the
+        # utterance's other beams: a slot that holds no hypothesis after the first step and is filled later needs them too)
+        x = self._decoder_hidden(st.enc, prompt, st.enc_lens_host, 0, cross_kv=st.cross_kv,
+                                 self_cache=st.self_kv if st.group == 1 else st.self_kv[:, ::st.group])
+        if st.group > 1:
+            kv = st.self_kv.view(st.self_kv.shape[0], B, st.group, st.cap, 2 * st.D)
+            kv[:, :, 1:, :P].copy_(kv[:, :, :1, :P].expand(-1, -1, st.group - 1, -1, -1))
         st.t = P
         with torch.cuda.device(self.device):
             if also_row is None:
@@ -542,20 +614,23 @@ class WhisperSeq2Seq:
         """ctx [B, D] of the one new row: ``kv`` [B, rows, 2 D] is a layer's cache (``kind`` "self": the first ``n_keys`` rows
         are in use) or its cross k|v ("cross": all S rows, the encoder lengths on top)."""
         D, nh = st.D, self.config.decoder_attention_heads
+        if kind == "cross" and st.group > 1:  # the beams of an utterance read its one cross k|v
+            return hip.dec_attention_step_grouped(q, kv[:, :, :D], kv[:, :, D:], n_keys, nh, st.group, klens=st.enc_lens, workspace=st.ws,
+                                                  ctx=st.ctx)
         if st.step_cross if kind == "cross" else (st.step_self_min_keys is not None and n_keys >= st.step_self_min_keys):
             return hip.dec_attention_step(q, kv[:, :, :D], kv[:, :, D:], n_keys, nh, klens=st.enc_lens if kind == "cross" else None,
                                           workspace=st.ws, ctx=st.ctx)
         rows = kv.shape[1]
-        kv2 = kv.reshape(st.B * rows, 2 * D)
+        kv2 = kv.reshape(kv.shape[0] * rows, 2 * D)
         if kind == "self":  # the causal mask of a query at position n_keys - 1 hides the unused rows of the cache
-            return hip.dec_attention_fwd(q, kv2[:, :D], kv2[:, D:], st.B, 1, rows, nh, causal=True, q_offset=n_keys - 1, ctx=st.ctx)
+            return hip.dec_attention_fwd(q, kv2[:, :D], kv2[:, D:], kv.shape[0], 1, rows, nh, causal=True, q_offset=n_keys - 1, ctx=st.ctx)
         return hip.dec_attention_fwd(q, kv2[:, :D], kv2[:, D:], st.B, 1, rows, nh, klens=st.enc_lens_host, ctx=st.ctx)
 
     def _gen_step(self, st: _GenState, h_in: torch.Tensor) -> torch.Tensor:
         """One token: ``h_in`` [B, D] bf16, the embedding row at position ``st.t`` (``ssak_dec_greedy_step``'s ``h_next``), through
         the layers against the cache and the cross buffer -> the logits [B, Vp] fp32 of that position.  Nothing is read back."""
         cfg = self.config
-        B, D, F, t = st.B, st.D, cfg.decoder_ffn_dim, st.t
+        B, D, F, t = st.B * st.group, st.D, cfg.decoder_ffn_dim, st.t  # (B: the step's rows)
         if t >= st.cap:
             raise ValueError(f"the cache of {st.cap} rows is full")
         lin = lambda a, w, bias, out, N, K, epi=hip.EPI_NONE: hip.gemm(a, w, out, B, N, K, lda=K, ldb=K, ldc=N, bias=bias, epilogue=epi)
@@ -574,7 +649,7 @@ class WhisperSeq2Seq:
                 hip.layernorm_fwd(st.y, h, self._f(p + "encoder_attn_layer_norm.weight"), self._f(p + "encoder_attn_layer_norm.bias"), h2, x)
                 h, h2 = h2, h
                 lin(x, self._w(p + "encoder_attn.q_proj.weight"), self._f(p + "encoder_attn.q_proj.bias"), st.q, D, D)
-                ctx = self._gen_attend(st, "cross", st.q, st.cross_kv[l].view(B, st.S, 2 * D), st.S)
+                ctx = self._gen_attend(st, "cross", st.q, st.cross_kv[l].view(st.B, st.S, 2 * D), st.S)
                 lin(ctx, self._w(p + "encoder_attn.out_proj.weight"), self._f(p + "encoder_attn.out_proj.bias"), st.y, D, D)
                 hip.layernorm_fwd(st.y, h, self._f(p + "final_layer_norm.weight"), self._f(p + "final_layer_norm.bias"), h2, x)
                 h, h2 = h2, h
@@ -586,6 +661,86 @@ class WhisperSeq2Seq:
             st.h, st.h2 = h, h2
             st.t = t + 1
             return self._project(x, B)
+
+    def _beam_begin(self, st: _GenState, P: int, n_max: int, eos: int, pad: int, sup, bsup, ts: Optional[dict]) -> _BeamState:
+        B, nb = st.B, st.group
+        R, dev = B * nb, self.device
+        with torch.cuda.device(dev):
+            sums = torch.full((B, nb), float("-inf"), dtype=torch.float32, device=dev)
+            sums[:, 0] = 0.0
+            i32 = lambda *shape, fill=0: torch.full(shape, fill, dtype=torch.int32, device=dev)
+            f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+            return _BeamState(B=B, nb=nb, P=P, eos=eos, pad=pad, sup=sup, bsup=bsup, ts=ts, tokens=i32(R, n_max, fill=pad), logprobs=f32(R, n_max),
+                              sums=sums, src=i32(R), ts_last=None if ts is None else i32(R, fill=-1), cand_token=i32(R, nb + 1, fill=-1),
+                              cand_logprob=torch.full((R, nb + 1), float("-inf"), dtype=torch.float32, device=dev),
+                              fin_tokens=i32(B, nb, n_max, fill=pad), fin_logprobs=f32(B, nb, n_max), fin_len=i32(B, nb), fin_sum=f32(B, nb),
+                              n_fin=i32(B), done=torch.zeros(B, dtype=torch.uint8, device=dev), n_unf=i32(1),
+                              h_next=torch.empty((R, st.D), dtype=torch.bfloat16, device=dev))
+
+    def _beam_step(self, st: _GenState, bs: _BeamState, logits: torch.Tensor, last: bool = False):
+        """One step of the beam search on ``logits`` [B * nb, Vp] (the prefill's logits repeated per beam, or :meth:`_gen_step`'s):
+        ``ssak_dec_beam_topk``, ``ssak_dec_beam_select`` and ``ssak_dec_kv_reorder`` over the cache rows that can differ between
+        the beams of an audio, [P, st.t): the prompt's rows [0, P) are the same in every beam since :meth:`_gen_prefill`.
+        ``bs.h_next`` is then the input of the next :meth:`_gen_step` (not formed when ``last``).  Nothing is read back."""
+        V, i = self.config.vocab_size, bs.i
+        tsk = {} if bs.ts is None else dict(timestamps=True, tokens=bs.tokens, ts_last=bs.ts_last, **bs.ts)
+        with torch.cuda.device(self.device):
+            hip.dec_beam_topk(logits, V, bs.nb, done=bs.done, cand_token=bs.cand_token, cand_logprob=bs.cand_logprob, eos_id=bs.eos, t=i,
+                              suppress=bs.sup, begin_suppress=bs.bsup, first=i == 0, **tsk)
+            hip.dec_beam_select(bs.cand_token, bs.cand_logprob, bs.nb, V, sum_logprob=bs.sums, src=bs.src, tokens=bs.tokens, logprobs=bs.logprobs,
+                                t=i, fin_tokens=bs.fin_tokens, fin_logprobs=bs.fin_logprobs, fin_len=bs.fin_len, fin_sum=bs.fin_sum, n_fin=bs.n_fin,
+                                done=bs.done, n_unfinished=bs.n_unf, eos_id=bs.eos, pad_id=bs.pad, ts_last=bs.ts_last,
+                                ts_begin=0 if bs.ts is None else bs.ts["ts_begin"], embed_tokens=self._w("embed_tokens.weight"),
+                                embed_positions=self._w("embed_positions.weight"), next_pos=bs.P + i, h_next=None if last else bs.h_next)
+            if not last and bs.nb > 1 and st.t > bs.P:
+                hip.dec_kv_reorder(st.self_kv, bs.src, bs.nb, bs.P, st.t)
+        bs.i = i + 1
+
+    def _generate_beam(self, st: _GenState, logits: torch.Tensor, P: int, n_max: int, eos: int, pad: int, sup, bsup, ts, poll_every: int,
+                       length_penalty, no_speech) -> GenerateResult:
+        """The loop of :meth:`generate` with ``beam_size``: lock step over B * nb rows, the host polls ``n_unfinished`` (audios that
+        do not hold nb finished sequences yet), one copy at the end, finalisation and ranking on the host."""
+        B, nb = st.B, st.group
+        bs = self._beam_begin(st, P, n_max, eos, pad, sup, bsup, ts)
+        with torch.cuda.device(self.device):
+            word = torch.zeros(1, dtype=torch.int32).pin_memory()
+            logits = logits.repeat_interleave(nb, dim=0)
+            for i in range(n_max):
+                last = i + 1 == n_max
+                self._beam_step(st, bs, logits, last=last)
+                if last:
+                    break
+                if poll_every and bs.i % poll_every == 0:
+                    word.copy_(bs.n_unf, non_blocking=True)
+                    torch.cuda.current_stream().synchronize()
+                    if int(word[0]) == 0:
+                        break
+                logits = self._gen_step(st, bs.h_next)
+            steps = bs.i
+            host = lambda x: x.cpu().numpy()
+            tok, lp, sums = host(bs.tokens).reshape(B, nb, -1), host(bs.logprobs).reshape(B, nb, -1), host(bs.sums)
+            ftok, flp, flen, fsum, nfin = host(bs.fin_tokens), host(bs.fin_logprobs), host(bs.fin_len), host(bs.fin_sum), host(bs.n_fin)
+            if no_speech is not None:
+                no_speech = np.exp(no_speech.double().cpu().numpy())
+        beams, beam_lps, chosen, chosen_lp, chosen_sum = [], [], [], [], []
+        for b in range(B):
+            cands = beam_finalize(tok[b], sums[b], ftok[b], flen[b], fsum[b], nfin[b], steps, nb)
+            w = beam_rank(cands, length_penalty)
+            lps = [(flp[b, k, :flen[b, k]] if fin else lp[b, k, :steps] if k >= 0 else lp[b, 0, :0]).astype(np.float64) for _, _, fin, k in cands]
+            beams.append([(c[0], c[1]) for c in cands])
+            beam_lps.append(lps)
+            chosen.append(cands[w][0])
+            chosen_sum.append(cands[w][1])
+            chosen_lp.append(lps[w])
+        lens = np.array([len(c) for c in chosen], dtype=np.int64)
+        n = int(lens.max())
+        tok_a, lp_a = np.full((B, n), pad, dtype=np.int32), np.zeros((B, n), dtype=np.float64)
+        for b in range(B):
+            tok_a[b, :lens[b]] = chosen[b]
+            lp_a[b, :lens[b]] = chosen_lp[b]
+        s = np.array(chosen_sum, dtype=np.float64)
+        return GenerateResult(tokens=chosen, lens=lens, token_array=tok_a, logprobs=lp_a, sum_logprob=s, avg_logprob=s / (lens + 1), steps=steps,
+                              no_speech_prob=no_speech, beams=beams, beam_logprobs=beam_lps)
 
     def _token_mask(self, ids, what: str) -> Optional[torch.Tensor]:
         """A list of token ids -> the uint8 [V] device mask ``ssak_dec_greedy_step`` reads (None for an empty list)."""
@@ -624,8 +779,8 @@ class WhisperSeq2Seq:
 
     def generate(self, enc_or_audio, prompt=None, language=None, task: str = "transcribe", max_new_tokens: Optional[int] = None, enc_lens=None,
                  suppress_tokens=None, begin_suppress_tokens=None, eos_token_id: Optional[int] = None, poll_every: int = 8,
-                 timestamps: bool = False) -> GenerateResult:
-        """Greedy transcription (temperature 0, no beam) of a batch in lock step -> :class:`GenerateResult`.
+                 timestamps: bool = False, beam_size: Optional[int] = None, length_penalty: Optional[float] = None) -> GenerateResult:
+        """Greedy transcription (temperature 0), or beam search with ``beam_size``, of a batch in lock step -> :class:`GenerateResult`.
 
         ``prompt`` [B, P] or [P] ids (one P for the batch); by default ``[<|startoftranscript|>, language, task,
         <|notimestamps|>]``, where ``language = None`` runs :meth:`detect_language`'s pass first (on this call's cross k|v buffer) and gives each
@@ -643,14 +798,28 @@ class WhisperSeq2Seq:
         ``timestamps=True``: whisper's timestamp rules (``ssak_dec_timestamp_step``; the first timestamp at most
         ``max_initial_timestamp_index``), the default prompt without ``<|notimestamps|>``, by default at most
         ``min(max_target_positions // 2, max_target_positions - P)`` tokens (whisper's ``sample_len``), and ``no_speech_prob``
-        in the result.  The default leaves the call as it was."""
+        in the result.  The default leaves the call as it was.
+
+        ``beam_size`` in [1, 8]: whisper's ``BeamSearchDecoder`` (DESIGN.md "Whisper beam search": no patience, no temperature
+        fallback) with ``MaximumLikelihoodRanker(length_penalty)``.  The prompt, the language pass and ``no_speech_prob`` run once
+        per utterance; the token step runs ``B * beam_size`` rows whose cross-attention shares the utterance's one cross k|v buffer;
+        the self-attention cache follows the hypotheses (``ssak_dec_kv_reorder``).  ``GenerateResult.beams`` lists every candidate.
+        ``beam_size=None`` is the greedy path, unchanged."""
         cfg = self.config
         timestamps = bool(timestamps)
+        if beam_size is not None:
+            beam_size = int(beam_size)
+            if not 1 <= beam_size <= 8:
+                raise ValueError(f"beam_size {beam_size}: 1 to 8 hypotheses per utterance are built")
+        elif length_penalty is not None:
+            raise ValueError("length_penalty ranks the candidates of a beam search: pass beam_size")
         if timestamps and cfg.no_timestamps_token_id is None:
             raise ValueError("timestamps=True: the model folder names no no_timestamps_token_id (generation_config.json), the timestamp ids are "
                              "those above it")
         enc = self._as_enc(enc_or_audio)
         B = enc.shape[0]
+        if beam_size is not None and B * beam_size > 65535:
+            raise ValueError(f"{B} utterances x beam_size {beam_size} = {B * beam_size} decoder rows: at most 65535 in one call")
         V, maxp = cfg.vocab_size, cfg.max_target_positions
         eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
         if eos is None:
@@ -678,7 +847,7 @@ class WhisperSeq2Seq:
             raise ValueError("poll_every must be >= 0")
         sup = self._token_mask(cfg.suppress_tokens if suppress_tokens is None else suppress_tokens, "suppress_tokens")
         bsup = self._token_mask(cfg.begin_suppress_tokens if begin_suppress_tokens is None else begin_suppress_tokens, "begin_suppress_tokens")
-        st = self._gen_begin(enc, enc_lens, cap=P + n_max)
+        st = self._gen_begin(enc, enc_lens, cap=P + n_max, group=1 if beam_size is None else beam_size)
         if detect:
             prompt = self.default_prompt(B, self._detect_language(enc, st.enc_lens_host, cross_kv=st.cross_kv)[0], task, timestamps)
         no_speech = None
@@ -695,6 +864,9 @@ class WhisperSeq2Seq:
             logits, no_speech = self._gen_prefill(st, prompt, also_row=sot_rows[0], also_target=ns_id)
         else:
             logits = self._gen_prefill(st, prompt)
+        if beam_size is not None:
+            ts = dict(ts_begin=ts_begin, no_timestamps_id=int(cfg.no_timestamps_token_id), max_initial=max_initial) if timestamps else None
+            return self._generate_beam(st, logits, P, n_max, eos, pad, sup, bsup, ts, poll_every, length_penalty, no_speech)
         E, Pz = self._w("embed_tokens.weight"), self._w("embed_positions.weight")
         with torch.cuda.device(self.device):
             tokens = torch.full((B, n_max), pad, dtype=torch.int32, device=self.device)

@@ -125,9 +125,10 @@ def seek_loop(content_frames: Sequence[int], decode_round, ts_begin: int, eos: i
 
 
 def transcribe(model, waveforms, language=None, task: str = "transcribe", no_speech_threshold: Optional[float] = 0.6,
-               logprob_threshold: Optional[float] = -1.0, batch_size: int = 8, _max_rounds: Optional[int] = None) -> List[TranscribeResult]:
+               logprob_threshold: Optional[float] = -1.0, batch_size: int = 8, beam_size: Optional[int] = None, _max_rounds: Optional[int] = None) -> List[TranscribeResult]:
     """``waveforms``: a list of 1-D 16 kHz waveforms of any length -> one :class:`TranscribeResult` per file.  ``language``: one code,
-    one per file, or None (detected on each file's first window).  ``batch_size`` files run in lock step at a time."""
+    one per file, or None (detected on each file's first window).  ``batch_size`` files run in lock step at a time.  ``beam_size``: every window is decoded by
+    ``generate(timestamps=True, beam_size=...)`` (None: greedy)."""
     import torch
     cfg = model.config
     if cfg.no_timestamps_token_id is None or cfg.eos_token_id is None:
@@ -167,7 +168,8 @@ def transcribe(model, waveforms, language=None, task: str = "transcribe", no_spe
                 if todo:
                     for i, code in zip(todo, model.detect_language(enc[todo])[0]):
                         langs[group[active[i]]] = code
-            r = model.generate(enc, language=[langs[group[a]] for a in active] if has_lang else None, task=task, timestamps=True)
+            r = model.generate(enc, language=[langs[group[a]] for a in active] if has_lang else None, task=task, timestamps=True,
+                               beam_size=beam_size)
             out = []
             for b in range(len(active)):
                 toks = r.tokens[b]
