@@ -429,10 +429,12 @@ def augment_fir_drop(x, taps=None, chunks=None, chunk_counts=None, chunk_counts_
     return out
 
 
-def lm_query(lm: NgramLMDesc, ctx_ids: torch.Tensor, words: torch.Tensor):
-    """log10 P(words[q] | ctx_ids[q]) with ARPA backoff (``ssak_lm_query``); ctx_ids [Q, order-1] int32, most recent last."""
+def lm_query(lm: NgramLMDesc, ctx_ids: torch.Tensor | None, words: torch.Tensor):
+    """log10 P(words[q] | ctx_ids[q]) with ARPA backoff (``ssak_lm_query``); ctx_ids [Q, order-1] int32, most recent last
+    (None for an order-1 LM, which has no context)."""
     words = words.to(dtype=torch.int32).contiguous()
-    ctx_ids = ctx_ids.to(device=words.device, dtype=torch.int32).contiguous()
+    if ctx_ids is not None:
+        ctx_ids = ctx_ids.to(device=words.device, dtype=torch.int32).contiguous()
     out = torch.empty(words.numel(), dtype=torch.float32, device=words.device)
     check(lib.ssak_lm_query(C.byref(lm), ptr(ctx_ids), ptr(words), words.numel(), ptr(out), stream()))
     return out

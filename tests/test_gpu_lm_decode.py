@@ -1,6 +1,8 @@
 """GPU: CTC beam search with an ARPA n-gram LM (ssak_ctc_lm_beam_decode / ssak_lm_query, ssak_amd.lm) against the host
-tables, greedy decoding, the exhaustive objective and the CPU restatement (tests/lm_beam_ref.py); determinism, argument
-checks, and ``python -m ssak_amd.infer --arpa`` end to end."""
+tables, greedy decoding, the exhaustive objective and the CPU restatement (tests/lm_beam_ref.py); the case table of
+tests/lm_cases.py (vocabulary strips, extra columns, candidate key storage, beam widths, exact ties, LM orders, a long
+utterance, -inf logits) against the float64 restatement; determinism, argument checks, and
+``python -m ssak_amd.infer --arpa`` end to end."""
 import dataclasses
 import os
 import subprocess
@@ -15,6 +17,8 @@ from ssak_amd.data import CharTokenizer
 from ssak_amd.lm import NgramLM, label_classes
 
 import lm_beam_ref as R
+import lm_cases as C
+from lm_cases import peaked as _peaked
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,26 +40,6 @@ def _decode(logits, lens, lm, **kw):
     ids, n, score = ids.cpu().numpy(), n.cpu().numpy(), score.cpu().numpy()
     assert (n >= 0).all()
     return [list(ids[b, :n[b]]) for b in range(len(n))], score, ids
-
-
-def _peaked(rng, text, conf=0.3, F=None):
-    """Posteriors of a label sequence: each label held 1-2 frames then blank, a confusable second label in some frames."""
-    labs = TOK.encode(text)
-    rows = []
-    for l in labs:
-        for _ in range(int(rng.integers(1, 3))):
-            r = rng.standard_normal(len(TOK)).astype(np.float32) * 0.5
-            r[l] += 9.0
-            if rng.random() < conf:
-                r[int(rng.integers(5, 31))] += 7.5
-            rows.append(r)
-        r = rng.standard_normal(len(TOK)).astype(np.float32) * 0.5
-        r[BLANK] += 8.0
-        rows.append(r)
-    x = np.stack(rows)
-    if F is not None:
-        x = np.concatenate([x, np.zeros((F - len(x), len(TOK)), np.float32)])
-    return x
 
 
 SENTENCES = ["bonjour le monde", "il est un petit chat", "merci bien", "dans la maison", "le chien et le chat",
@@ -100,16 +84,16 @@ def test_width_one_without_lm_equals_greedy(tiny):
     assert [len(g) for g in got] == list(g_n) and got[0] == [] and len(got[1]) <= 1
 
 
-def test_exhaustive_objective_small(tmp_path):
-    """T = 4, labels {blank, |, a, b}, beam 256 (holds every (prefix, last)), pruning off: the exhaustive argmax."""
+def _exhaustive_objective(tmp_path, order):
     from ssak_amd import lm as L
-    tok = CharTokenizer(["<pad>", "|", "a", "b"])
+    tok = CharTokenizer(["<pad>", "|", "a", "b", "<s>"])
     cls = label_classes(tok)
-    synth.write_arpa(str(tmp_path / "ab.arpa"), ["a", "b", "ab", "ba", "aa", "bab"], [20, 20], seed=2)
+    synth.write_arpa(str(tmp_path / "ab.arpa"), ["a", "b", "ab", "ba", "aa", "bab"], [20] * (order - 1), seed=2)
     lm = NgramLM(str(tmp_path / "ab.arpa"), tok).to("cuda:0")
+    assert lm.order == order
     rng = np.random.default_rng(2)
-    B, T = 6, 4
-    x = (rng.standard_normal((B, T, 4)) * 2).astype(np.float32)
+    B, T = 6, 5
+    x = (rng.standard_normal((B, T, 5)) * 2).astype(np.float32)
     ids, n, score = L.decode(torch.from_numpy(x).cuda(), torch.full((B,), T, dtype=torch.int32), lm, tok, alpha=0.7, beta=0.5,
                              beam_width=256, beam_prune_logp=-np.inf, token_min_logp=-np.inf)
     ids, n, score = ids.cpu().numpy(), n.cpu().numpy(), score.cpu().numpy()
@@ -118,6 +102,18 @@ def test_exhaustive_objective_small(tmp_path):
         got = list(ids[b, :n[b]])
         assert got == want or R.objective(x[b], T, got, lm, cls, 0, 0.7, 0.5) >= best - 1e-5 * abs(best), (b, got, want)
         assert float(score[b]) == pytest.approx(best, rel=1e-4, abs=1e-4)
+
+
+def test_exhaustive_objective_small(tmp_path):
+    """T = 5, labels {blank, |, a, b, <s> (a label without text)}, beam 256, pruning off: the exhaustive argmax.  (The beam
+    no longer holds every (prefix, last) in the last frame; what it drops is far below the winner.)"""
+    _exhaustive_objective(tmp_path, 3)
+
+
+@pytest.mark.parametrize("order", [1, 6])
+def test_exhaustive_objective_small_other_orders(tmp_path, order):
+    """The same with a unigram LM (no context, no n-gram table) and with an order-6 LM (all five context slots)."""
+    _exhaustive_objective(tmp_path, order)
 
 
 @pytest.mark.parametrize("W", [1, 8, 100, 256])
@@ -254,3 +250,197 @@ def test_infer_cli_with_arpa(tmp_path):
     (tmp_path / "bin.arpa").write_bytes(b"mmap lm http://kheafield.com/code format version 5\n\0\0\0\1")
     r = subprocess.run(cmd + ["--arpa", str(tmp_path / "bin.arpa")], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode != 0 and "not an ARPA text file" in r.stderr
+
+
+# ------------------------------------------------------------------------------------------------- the case table (tests/lm_cases.py)
+_REF = {}
+
+
+def _reference(built):
+    """The float64 / float32 analysis of a case's utterances, computed once per case."""
+    name = built.case["name"]
+    if name not in _REF:
+        _REF[name] = [C.analyse(built, u) for u in range(len(built.x))]
+    return _REF[name]
+
+
+def _decode_case(built, x=None, lens=None, workspace=None):
+    """-> (ids [B, F], n [B], score [B]) numpy, through hip.ctc_lm_beam_decode as ssak_amd.lm.decode calls it."""
+    from ssak_amd import hip
+    x = built.x if x is None else x
+    lens = built.lens if lens is None else lens
+    lm = built.lm.to("cuda:0") if built.lm.device is None else built.lm
+    cls = torch.from_numpy(built.cls).cuda()
+    ids, n, score = hip.ctc_lm_beam_decode(torch.from_numpy(np.ascontiguousarray(x)).cuda(), torch.tensor(lens, dtype=torch.int32),
+                                           lm.desc, n_labels=len(built.tok), blank=built.blank, label_class=cls,
+                                           unk_score_offset=-10.0, workspace=workspace, **built.kw)
+    torch.cuda.synchronize()
+    ids, n, score = ids.cpu().numpy(), n.cpu().numpy(), score.cpu().numpy()
+    assert (n >= 0).all()
+    return ids, n, score
+
+
+def _check_case(built, ids, n, score):
+    """A decisive case: the float64 restatement's transcript exactly, its score to 1e-4.  Otherwise the equivalence check
+    of test_matches_restatement_on_flat_logits: score to 1e-3, a different transcript as good under the exact objective."""
+    case = built.case
+    for u, a in enumerate(_reference(built)):
+        got = [int(v) for v in ids[u, :n[u]]]
+        print(f"LMCASE {case['name']} u{u}: margin {a['margin']:.3e} noise {a['noise']:.3e} decisive {a['decisive']} "
+              f"|device - f64| {abs(float(score[u]) - a['score']):.3e} = {abs(float(score[u]) - a['score']) / a['noise']:.2f} x noise, "
+              f"same transcript {got == a['ids']}")
+        assert a["decisive"] == case["decisive"]
+        if case["decisive"]:
+            assert got == a["ids"], (case["name"], u, got, a["ids"])
+            assert float(score[u]) == pytest.approx(a["score"], rel=1e-4)
+        else:
+            assert float(score[u]) == pytest.approx(a["score"], rel=1e-3)
+            if got != a["ids"]:
+                args = (built.lm, built.cls, built.blank, built.kw["alpha"], built.kw["beta"])
+                og = R.objective(built.x[u], built.lens[u], got, *args)
+                ow = R.objective(built.x[u], built.lens[u], a["ids"], *args)
+                assert og == pytest.approx(ow, rel=1e-3)
+
+
+def _names(prefix):
+    return [c["name"] for c in C.CASES if c["name"].startswith(prefix)]
+
+
+@pytest.mark.parametrize("name", _names("strip"))
+def test_label_strips(tmp_path, name):
+    """5 .. 1024 labels: the log-softmax, argmax and S_t compaction over one to four strips of 256 labels (strip1024_all:
+    token_min_logp = -inf, so S_t is all 1024 labels and fills across the four strips)."""
+    built = C.build(C.BY_NAME[name], tmp_path)
+    _check_case(built, *_decode_case(built))
+
+
+@pytest.mark.parametrize("name", _names("extra"))
+def test_extra_columns_are_not_read(tmp_path, name):
+    """n_labels < V with +50 in the surplus columns: the same bits as the run on the first n_labels columns alone."""
+    built = C.build(C.BY_NAME[name], tmp_path)
+    NL = built.case["n_labels"]
+    assert built.x.shape[2] > NL and (built.x[:, :, NL:] == 50.0).all()
+    ids, n, score = _decode_case(built)
+    ids2, n2, score2 = _decode_case(built, x=built.x[:, :, :NL])
+    assert np.array_equal(ids, ids2) and np.array_equal(n, n2) and np.array_equal(score.view(np.uint32), score2.view(np.uint32))
+    _check_case(built, ids, n, score)
+
+
+@pytest.mark.parametrize("name", _names("keys"))
+def test_candidate_key_storage(tmp_path, name):
+    """W * n_labels = 4096 (keys in LDS), 4097 and 9600 (keys in the workspace), pruning off so that every beam x label is
+    a candidate; the workspace is exactly ssak_ctc_lm_beam_workspace_bytes() bytes inside a larger buffer whose bytes in
+    front of it and behind it must stay as they were."""
+    from ssak_amd import hip
+    built = C.build(C.BY_NAME[name], tmp_path)
+    B, F, V = built.x.shape
+    need = hip.lib.ssak_ctc_lm_beam_workspace_bytes(B, F, V, built.case["W"])
+    guard = 4096
+    big = torch.full((need + 2 * guard,), 0xA5, dtype=torch.uint8, device="cuda:0")
+    ws = big[guard:guard + need]
+    assert ws.numel() == need and ws.data_ptr() % 256 == 0
+    ids, n, score = _decode_case(built, workspace=ws)
+    big = big.cpu().numpy()
+    assert (big[:guard] == 0xA5).all() and (big[guard + need:] == 0xA5).all()
+    assert (big[guard:guard + need] != 0xA5).any()
+    assert _reference(built)[0]["max_kept"] == built.case["W"]
+    _check_case(built, ids, n, score)
+
+
+@pytest.mark.parametrize("name", _names("width"))
+def test_beam_width_edges(tmp_path, name):
+    """W = 2, 63, 64, 65, 255, 256 on peaked posteriors: the beam fills (asserted on the restatement), so tid < take, the
+    rank-by-count sort and the scans run at and across the wave boundaries."""
+    built = C.build(C.BY_NAME[name], tmp_path)
+    assert _reference(built)[0]["max_kept"] == built.case["W"]
+    _check_case(built, *_decode_case(built))
+
+
+@pytest.mark.parametrize("name", _names("tie"))
+def test_exact_ties_go_to_the_smaller_index(tmp_path, name):
+    """Every non-blank label has the same logit in a frame and most labels begin no LM word, so whole groups of candidates
+    have bit-identical totals in any arithmetic and a group straddles the cutoff (asserted on the restatement): the
+    survivors are the lowest enumeration indices, hence the restatement's transcript (tie*_empty: two labels without text
+    with identical columns)."""
+    built = C.build(C.BY_NAME[name], tmp_path)
+    x = built.x[0]
+    assert all(len({float(v) for i, v in enumerate(row) if i != built.blank}) == 1 for row in x)
+    assert _reference(built)[0]["tie_cutoffs"] >= 1
+    _check_case(built, *_decode_case(built))
+
+
+@pytest.mark.parametrize("name", ["order1", "order2", "order3", "order6"])
+def test_lm_orders(tmp_path, name):
+    """Orders 1 (no context), 2, 3 and 6 (SSAK_LM_MAX_ORDER: all five context slots) on a ten-word sentence, one word OOV."""
+    built = C.build(C.BY_NAME[name], tmp_path)
+    assert built.lm.order == built.case["order"]
+    ids, n, score = _decode_case(built)
+    text = built.tok.decode(ids[0, :n[0]], group_tokens=False).split()
+    assert len(text) >= 10 and sum(w not in built.lm.word_id for w in text) >= 1
+    _check_case(built, ids, n, score)
+
+
+def test_long_context_changes_the_transcript(tmp_path):
+    """The order-6 LM and the same file cut to its bigrams, same acoustics: one word differs, by the long context alone."""
+    out = []
+    for name in ("order6", "order2t"):
+        built = C.build(C.BY_NAME[name], tmp_path)
+        ids, n, score = _decode_case(built)
+        _check_case(built, ids, n, score)
+        out.append(built.tok.decode(ids[0, :n[0]], group_tokens=False).split())
+    assert len(out[0]) == len(out[1]) and sum(a != b for a, b in zip(*out)) == 1
+
+
+@pytest.mark.parametrize("order", [1, 2, 6])
+def test_lm_query_other_orders(tmp_path, order):
+    """ssak_lm_query at orders 1 (null context), 2 and 6 against NgramLM.log10p, bit for bit; ids >= n_words give NaN."""
+    from ssak_amd import hip
+    rng = np.random.default_rng(order)
+    words = synth.synth_words(rng, 500)
+    synth.write_arpa(str(tmp_path / "q.arpa"), words, [4000] * (order - 1), seed=order)
+    lm = NgramLM(str(tmp_path / "q.arpa"), TOK, max_load=0.97).to("cuda:0")
+    assert lm.order == order
+    Q, nw, nc = 20_000, len(lm.words), order - 1
+    ctx = rng.integers(0, nw, (Q, nc)).astype(np.int32)
+    w = rng.integers(0, nw, Q).astype(np.int32)
+    if order > 1:  # a third along stored n-grams of the highest order, some with missing older words
+        top = lm.ng_keys[-1]
+        top = top[top[:, 0] >= 0]
+        sel = rng.integers(0, len(top), Q // 3)
+        ctx[:Q // 3], w[:Q // 3] = top[sel, :nc], top[sel, nc]
+        for q in range(Q // 3, Q // 3 + 3000):
+            ctx[q, :int(rng.integers(1, nc + 1))] = -1
+    bad = np.arange(Q - 200, Q)
+    w[bad[:100]] = nw + rng.integers(0, 5, 100)
+    if order > 1:
+        ctx[bad[100:], rng.integers(0, nc, 100)] = nw + rng.integers(0, 5, 100)
+    else:
+        w[bad[100:]] = nw
+    got = hip.lm_query(lm.desc, torch.from_numpy(ctx).cuda() if order > 1 else None, torch.from_numpy(w).cuda()).cpu().numpy()
+    assert np.isnan(got[bad]).all()
+    good = np.arange(Q - 200)
+    want = np.array([lm.log10p(list(ctx[q]), int(w[q])) for q in good], dtype=np.float32)
+    assert np.array_equal(got[good].view(np.uint32), want.view(np.uint32))
+
+
+def test_long_utterance(tmp_path):
+    """F = 1500, W = 16, lengths (1500, 1371): the node store 1 + F * W, the prefix hash as it grows, transcripts of ~600
+    labels and their read-back; n is the winner's depth, ids[n:] = -1, and the result is that of the utterance alone."""
+    built = C.build(C.BY_NAME["long"], tmp_path)
+    ids, n, score = _decode_case(built)
+    _check_case(built, ids, n, score)
+    for u, L in enumerate(built.lens):
+        assert 400 < n[u] <= L and (ids[u, :n[u]] >= 0).all() and (ids[u, n[u]:] == -1).all()
+        if built.case["decisive"]:
+            assert n[u] == len(_reference(built)[u]["ids"])
+    i1, n1, s1 = _decode_case(built, x=built.x[1:2, :built.lens[1]], lens=[built.lens[1]])
+    assert n1[0] == n[1] and np.array_equal(i1[0, :n1[0]], ids[1, :n[1]]) and (i1[0, n1[0]:] == -1).all()
+    assert s1.view(np.uint32)[0] == score.view(np.uint32)[1]
+
+
+def test_masked_columns(tmp_path):
+    """-inf logits: a third of the non-blank columns in every frame (lp = the floor ln 1e-15), all but the blank in one."""
+    built = C.build(C.BY_NAME["masked"], tmp_path)
+    x = built.x[0]
+    assert np.isneginf(x).sum(axis=1).min() >= 10 and np.isneginf(x).sum(axis=1).max() == x.shape[1] - 1
+    _check_case(built, *_decode_case(built))

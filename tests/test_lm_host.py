@@ -10,6 +10,7 @@ from ssak_amd.data import CharTokenizer
 from ssak_amd.lm import LN10, NgramLM, label_classes, read_arpa
 
 import lm_beam_ref as R
+import lm_cases as C
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TINY = os.path.join(ROOT, "tests", "golden", "lm_tiny.arpa")
@@ -145,3 +146,51 @@ def test_lm_term_prefers_the_lm_word(tiny):
     assert good > bad
     want = 0.5 * float(LN10) * (-0.3 - 0.1 - 0.2 - 0.3) + 3 * 1.0  # P(bonjour|<s>) P(le|<s> bonjour) P(monde|..) P(</s>|le monde)
     assert float(good) == pytest.approx(want, rel=1e-6)
+
+
+# ------------------------------------------------------------------------------------------------- the shared case table
+@pytest.mark.parametrize("case", C.CASES, ids=lambda c: c["name"])
+def test_case_float32_restatement_agrees_with_float64(tmp_path, case, record_property):
+    """Every case of tests/lm_cases.py (the GPU tests decode the same): the float32 and float64 restatements return the same
+    transcript and scores within 1e-4; margin, fp32 noise and the decisive flag are those the table records (the margin is
+    float64 arithmetic: 1 %; the noise depends on the host's float32 exp / log: a factor of 2); one run takes < 3 s."""
+    b = C.build(case, tmp_path)
+    runs = [C.analyse(b, u) for u in range(len(b.x))]
+    for u, a in enumerate(runs):
+        print(f"{case['name']} u{u}: margin {a['margin']:.3e} noise {a['noise']:.3e} ratio {a['margin'] / max(a['noise'], 1e-30):.0f} "
+              f"decisive {a['decisive']} kept {a['max_kept']} tie cutoffs {a['tie_cutoffs']} seconds {a['seconds'][0]:.2f} {a['seconds'][1]:.2f}")
+        assert a["ids32"] == a["ids"] and a["split"] is None
+        assert a["score32"] == pytest.approx(a["score"], rel=1e-4)
+        assert max(a["seconds"]) < 3.0
+    w = C.worst(runs)
+    record_property("margin", w["margin"])
+    record_property("noise", w["noise"])
+    record_property("decisive", w["decisive"])
+    margin, noise, decisive = C.table_row(case["name"])
+    assert all(a["decisive"] for a in runs) == case["decisive"] == decisive
+    assert w["margin"] == pytest.approx(margin, rel=1e-2) and noise / 2 <= w["noise"] <= noise * 2
+    if case["kind"] == "width":
+        assert w["max_kept"] == case["W"]  # the beam fills
+    if b.ties:
+        assert w["tie_cutoffs"] >= 1  # a tied group straddles the cutoff
+        wrong, _ = R.beam_decode(b.x[0], b.lens[0], b.lm, b.cls, b.blank, dtype=np.float64, ties=True, tie_sign=-1, **b.kw)
+        assert wrong != w["ids"]  # and the opposite tie rule would show in the transcript
+
+
+def test_case_table_covers_the_edges():
+    by = C.BY_NAME
+    assert {by[n]["n_labels"] for n in by if n.startswith("strip")} == {5, 64, 65, 256, 257, 300, 1024}
+    assert {by[n]["W"] for n in by if n.startswith("width")} == {2, 63, 64, 65, 255, 256}
+    assert [by[n]["W"] * by[n]["n_labels"] for n in ("keys4096", "keys4097", "keys9600")] == [4096, 4097, 9600]
+    assert sum(not c["decisive"] for c in C.CASES) <= 3
+    assert all(c["decisive"] for c in C.CASES if c["name"] not in ("long", "keys4096", "keys4097", "keys9600"))
+
+
+def test_long_context_changes_the_transcript(tmp_path):
+    """The order-6 LM and the same file cut to its bigrams decode the same acoustics differently (one word)."""
+    b6, b2 = C.build(C.BY_NAME["order6"], tmp_path), C.build(C.BY_NAME["order2t"], tmp_path)
+    assert np.array_equal(b6.x, b2.x) and b6.lm.order == 6 and b2.lm.order == 2
+    assert np.array_equal(b6.lm.uni, b2.lm.uni) and np.array_equal(b6.lm.ng_val[0], b2.lm.ng_val[0])
+    t6 = b6.tok.decode(C.analyse(b6)["ids"], group_tokens=False).split()
+    t2 = b2.tok.decode(C.analyse(b2)["ids"], group_tokens=False).split()
+    assert len(t6) == len(t2) >= 10 and sum(x != y for x, y in zip(t6, t2)) == 1
