@@ -153,7 +153,6 @@ __device__ __forceinline__ float head_drop(float x, uint32_t rowkey, uint32_t co
 }
 
 constexpr int HEAD_BT = 8;  // utterances per pass over a weight row
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // out[b, j] = act(sum_k drop(in[b, k]) W[j, k] + bias[j]): one wave per output feature j streams its weight row once per
 // HEAD_BT utterances; lanes take float4 slices of the row, the wave total is the fixed-order DPP sum.

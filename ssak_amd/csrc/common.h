@@ -41,6 +41,7 @@ void ssak_set_error(const char* fmt, ...);
   } while (0)
 
 static inline int ssak_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 #ifdef __HIPCC__
 // Wave-wide reductions by DPP (quad swaps, row half mirror / mirror, row_bcast15 / 31, then v_readlane of lane 63): six

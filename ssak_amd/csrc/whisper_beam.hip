@@ -3,10 +3,11 @@
 // in ABI 610 / 620 no entry takes a host mirror of a device array or reads anything back, sums are fp32 in a fixed order and the
 // only atomics are integer ones.
 //
-// dec_beam_topk_kernel.  One workgroup per row of logits [B * nb, ldv].  The column predicate is dec_timestamp_kernel's (whisper_step.h:
+// dec_beam_topk_kernel.  One workgroup per row of logits [B * nb, ldv].  The column predicate is the token step's (whisper_step.h:
 // ts_rules, ts_mass_wins; without timestamps: the suppress masks alone), evaluated on the row's own history.  Pass one and two are
-// that kernel's: the text and the timestamp maximum with their lowest columns, then the two sums of exp(x - M) in column order.  The
-// mass decision fixes the candidate set (the timestamps alone, or every allowed column) and the log-sum.  Pass one also keeps, per
+// dec_token_step_kernel's, on the same scan_allowed: the text and the timestamp maximum with their lowest columns, then the two
+// sums of exp(x - M) in column order.  The mass decision fixes the candidate set (the timestamps alone, or every allowed
+// column) and the log-sum.  Pass one also keeps, per
 // thread, the L >= K best text columns and the L best timestamp columns in two sorted register lists (compile-time indices only;
 // equal values stay in column order); K rounds of block_argmax over the threads' better heads then give the candidates in the
 // order (value descending, column ascending), the owner of each dropping it from its list.  The row is read twice, as before.
@@ -25,7 +26,6 @@
 #include "whisper_step.h"
 
 namespace {
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 constexpr int BM_MAX_NB = 8;
 constexpr int BM_MAX_K = BM_MAX_NB + 1;
 constexpr int BM_MAX_CAND = BM_MAX_NB * BM_MAX_K;
@@ -44,26 +44,6 @@ struct TkParams {
   long ldv, ldt;
   int V, nb, K, t, eos_id, timestamps, ts_begin, no_timestamps_id, max_initial;
 };
-
-// f(column, value) on every column of the row that no mask byte hits and the rules allow; a thread's columns come in increasing order
-template <bool VEC, typename F>
-__device__ __forceinline__ void scan_allowed(const float* x, const uint8_t* s0, const uint8_t* s1, int V, const TsRules& rules, F f) {
-  const int tid = threadIdx.x;
-  const int n4 = VEC ? (V & ~3) : 0;
-  for (int i = tid * 4; i < n4; i += GS_THREADS * 4) {
-    const float4 q = *reinterpret_cast<const float4*>(x + i);
-    uint32_t mk = s0 ? *reinterpret_cast<const uint32_t*>(s0 + i) : 0u;
-    if (s1) mk |= *reinterpret_cast<const uint32_t*>(s1 + i);
-    const float v[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (!((mk >> (8 * e)) & 0xffu) && rules.allowed(i + e)) f(i + e, v[e]);
-  }
-  for (int i = n4 + tid; i < V; i += GS_THREADS) {
-    const bool sup = (s0 && s0[i]) || (s1 && s1[i]);
-    if (!sup && rules.allowed(i)) f(i, x[i]);
-  }
-}
 
 // A thread's L best (value, column) pairs of one kind, highest first, in registers: every index below is a compile-time constant.
 template <int L>
@@ -112,7 +92,7 @@ __global__ __launch_bounds__(GS_THREADS) void dec_beam_topk_kernel(const TkParam
   int32_t* const out_t = p.cand_token + (long)row * K;
   float* const out_l = p.cand_logprob + (long)row * K;
 
-  // pass one: the thread's L best text and L best timestamp columns; their heads are dec_timestamp_kernel's four running statistics
+  // pass one: the thread's L best text and L best timestamp columns; their heads are dec_token_step_kernel's four running statistics
   TopList<L> lt, ls;
   lt.clear(), ls.clear();
   scan_allowed<VEC>(x, s0, s1, V, rules, [&](int c, float v) {
@@ -367,7 +347,7 @@ extern "C" int ssak_dec_beam_topk(const float* logits, long ldv, int B, int nb, 
   p.V = V, p.nb = nb, p.K = K, p.t = t, p.eos_id = eos_id, p.timestamps = timestamps ? 1 : 0, p.ts_begin = ts_begin;
   p.no_timestamps_id = no_timestamps_id, p.max_initial = max_initial < 0 ? -1 : max_initial;
   const hipStream_t st = (hipStream_t)stream;
-  const bool vec = aligned16(logits) && ldv % 4 == 0 && ((uintptr_t)p.suppress & 3) == 0 && ((uintptr_t)p.begin_suppress & 3) == 0;
+  const bool vec = scan_vec(logits, ldv, p.suppress, p.begin_suppress);
   // (the lists are 6 deep up to nb = 5, whisper's default and the reference's --accurate, and 9 deep beyond)
   if (vec && K <= 6)
     dec_beam_topk_kernel<true, 6><<<B * nb, GS_THREADS, 0, st>>>(p);
@@ -396,13 +376,7 @@ extern "C" int ssak_dec_beam_select(const int32_t* cand_token, const float* cand
   SSAK_REQUIRE(t >= 0 && t < ldt, "dec_beam_select: step t=%d outside the token buffer's %ld columns", t, ldt);
   SSAK_REQUIRE(t <= BM_MAX_T, "dec_beam_select: step t=%d, the histories of at most %d entries per beam fit the kernel", t, BM_MAX_T);
   if (ts_last) SSAK_REQUIRE(ts_begin > eos_id && ts_begin < V, "dec_beam_select: ts_begin=%d must lie in (eos_id=%d, V=%d)", ts_begin, eos_id, V);
-  if (h_next) {
-    SSAK_REQUIRE(embed_tokens && embed_positions, "dec_beam_select: h_next needs the two embedding tables");
-    SSAK_REQUIRE(D > 0 && D % 8 == 0 && max_positions > 0, "dec_beam_select: bad shape D=%d max_positions=%d", D, max_positions);
-    SSAK_REQUIRE(next_pos >= 0 && next_pos < max_positions, "dec_beam_select: next_pos=%d overruns the position table of %d", next_pos,
-                 max_positions);
-    SSAK_REQUIRE(aligned16(embed_tokens) && aligned16(embed_positions) && aligned16(h_next), "dec_beam_select: a buffer is not 16-byte aligned");
-  }
+  if (const int rc = check_h_next("dec_beam_select", embed_tokens, embed_positions, D, max_positions, next_pos, h_next)) return rc;
   SlParams p;
   p.cand_token = cand_token, p.cand_logprob = cand_logprob, p.sum_logprob = sum_logprob, p.src = src, p.tokens = tokens, p.logprobs = logprobs;
   p.ts_last = ts_last, p.fin_tokens = fin_tokens, p.fin_logprobs = fin_logprobs, p.fin_len = fin_len, p.fin_sum = fin_sum, p.n_fin = n_fin;

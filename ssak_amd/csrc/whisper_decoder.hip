@@ -20,8 +20,6 @@
 #include "kernels.h"
 
 namespace {
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // ---- ssak_dec_embed ----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void dec_embed_kernel(const bf16* __restrict__ tok, const bf16* __restrict__ pos,
                                                         const int32_t* __restrict__ ids, long rows, int L, int D, int V, int pos_offset,

@@ -17,25 +17,24 @@
 // ssak_dec_attention_step_grouped) query row b reads the keys and klens of utterance b / group: the beams of an audio share its
 // cross k|v buffer.
 //
-// dec_greedy_kernel.  One workgroup per row, the two-pass shape of token_logprobs_kernel with the suppress masks applied as the
-// columns are read.
-//
-// dec_timestamp_kernel (ABI 620).  dec_greedy_kernel with whisper's ApplyTimestampRules folded into the column predicate.  The
-// rules of a row reduce to uniform scalars read before the loop -- the two tokens the kernel itself wrote at columns t - 1 and
-// t - 2, and ts_last[b] -- that give one text interval [text_lo, ts_begin) and one timestamp interval [ts_lo, ts_hi]; a column
-// is allowed when no mask byte hits it, it is not <|notimestamps|> and it lies in one of the two.  No per-row mask exists in
-// memory.  Pass one carries four running statistics per thread (the text and the timestamp maximum, each with its lowest
-// column), pass two the two sums of exp(x - M) in column order; lanes, then waves, in a fixed order.
+// dec_token_step_kernel<VEC, TS>.  One workgroup per row, the two-pass shape of token_logprobs_kernel with the suppress masks applied
+// as the columns are read (whisper_step.h: scan_allowed, the loop dec_beam_topk_kernel runs).  Without TS it is the greedy step
+// (ABI 610): one running maximum with its lowest column, one sum; the rules' type is NoRules and nothing of them is compiled in.
+// With TS (ABI 620) whisper's ApplyTimestampRules are folded into the column predicate.  The rules of a row reduce to uniform
+// scalars read before the loop -- the two tokens the kernel itself wrote at columns t - 1 and t - 2, and ts_last[b] -- that give
+// one text interval [text_lo, ts_begin) and one timestamp interval [ts_lo, ts_hi]; a column is allowed when no mask byte hits it,
+// it is not <|notimestamps|> and it lies in one of the two.  No per-row mask exists in memory.  Pass one carries four running
+// statistics per thread (the text and the timestamp maximum, each with its lowest column), pass two the two sums of exp(x - M)
+// in column order; lanes, then waves, in a fixed order.
 #include <limits.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "kernels.h"
 #include "whisper_step.h"
 
 namespace {
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // ---- ssak_dec_attention_step -------------------------------------------------------------------------------------------------
 constexpr int AS_HD = 64;
 constexpr int AS_WAVES = 4;
@@ -194,9 +193,8 @@ void choose_split(int bh, int n_keys, int n_split, int* ns, int* chunk) {
   *ns = ssak_cdiv(n_keys, ch);
 }
 
-// ---- ssak_dec_greedy_step ----------------------------------------------------------------------------------------------------
-// (GS_THREADS, the timestamp rules and block_argmax: whisper_step.h, shared with whisper_beam.hip)
-
+// ---- ssak_dec_greedy_step, ssak_dec_timestamp_step ---------------------------------------------------------------------------
+// (GS_THREADS, the timestamp rules, scan_allowed, block_argmax and form_h_next: whisper_step.h, shared with whisper_beam.hip)
 struct GsParams {
   const float* logits;
   const uint8_t* suppress;
@@ -210,189 +208,59 @@ struct GsParams {
   bf16* h_next;
   long ldv, ldt;
   int V, D, t, next_pos, eos_id, pad_id;
-};
-
-template <bool VEC>
-__global__ __launch_bounds__(GS_THREADS) void dec_greedy_kernel(const GsParams p) {
-  __shared__ float red[16];
-  __shared__ int32_t ired[16];
-  const int tid = threadIdx.x, row = blockIdx.x;
-  const float* x = p.logits + (long)row * p.ldv;
-  const uint8_t* const s0 = p.suppress;
-  const uint8_t* const s1 = p.begin_suppress;
-  const bool was_finished = p.finished[row] != 0;  // (read by every thread before thread 0 writes it, behind the barriers below)
-  int token = p.pad_id;
-  float logprob = 0.f;
-  if (!was_finished) {  // (uniform over the workgroup)
-    const int V = p.V;
-    const int n4 = VEC ? (V & ~3) : 0;
-    float best = -INFINITY;
-    int32_t bi = INT_MAX;
-    for (int i = tid * 4; i < n4; i += GS_THREADS * 4) {
-      const float4 f = *reinterpret_cast<const float4*>(x + i);
-      uint32_t mk = s0 ? *reinterpret_cast<const uint32_t*>(s0 + i) : 0u;
-      if (s1) mk |= *reinterpret_cast<const uint32_t*>(s1 + i);
-      const float v[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (!((mk >> (8 * e)) & 0xffu) && v[e] > best) {  // strict: within a thread's increasing columns the first maximum stays
-          best = v[e];
-          bi = i + e;
-        }
-    }
-    for (int i = n4 + tid; i < V; i += GS_THREADS) {
-      const bool sup = (s0 && s0[i]) || (s1 && s1[i]);
-      const float v = x[i];
-      if (!sup && (v > best || (v == best && i < bi))) {
-        best = v;
-        bi = i;
-      }
-    }
-    // the lowest id that attains the maximum: lanes, then waves
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const float ov = __shfl_xor(best, o);
-      const int32_t oi = __shfl_xor(bi, o);
-      if (ov > best || (ov == best && oi < bi)) {
-        best = ov;
-        bi = oi;
-      }
-    }
-    if ((tid & 63) == 0) {
-      red[tid >> 6] = best;
-      ired[tid >> 6] = bi;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ww = 0; ww < GS_THREADS / 64; ++ww) {
-      const float ov = red[ww];
-      const int32_t oi = ired[ww];
-      if (ov > best || (ov == best && oi < bi)) {
-        best = ov;
-        bi = oi;
-      }
-    }
-    if (bi < V) {  // (a row whose columns are all suppressed, the caller's error, emits pad_id with log-prob 0)
-      float s = 0.f;
-      for (int i = tid * 4; i < n4; i += GS_THREADS * 4) {
-        const float4 f = *reinterpret_cast<const float4*>(x + i);
-        uint32_t mk = s0 ? *reinterpret_cast<const uint32_t*>(s0 + i) : 0u;
-        if (s1) mk |= *reinterpret_cast<const uint32_t*>(s1 + i);
-        const float v[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s += ((mk >> (8 * e)) & 0xffu) ? 0.f : expf(v[e] - best);
-      }
-      for (int i = n4 + tid; i < V; i += GS_THREADS) {
-        const bool sup = (s0 && s0[i]) || (s1 && s1[i]);
-        s += sup ? 0.f : expf(x[i] - best);
-      }
-      s = block_sum(s, red);
-      token = bi;
-      logprob = -logf(s);  // x[token] = the maximum: log-softmax = (best - best) - log s
-    }
-  }
-  if (tid == 0) {
-    p.tokens[(long)row * p.ldt + p.t] = token;
-    p.logprobs[(long)row * p.ldt + p.t] = logprob;
-    const bool now_finished = was_finished || token == p.eos_id;
-    p.finished[row] = now_finished ? 1 : 0;
-    if (!now_finished) atomicAdd(p.n_unfinished, 1);  // (an integer count on the word the entry zeroed: order-free)
-  }
-  if (p.h_next) form_h_next(p.h_next + (long)row * p.D, p.embed_tokens, p.embed_positions, token, p.V, p.D, p.next_pos);
-}
-
-// ---- ssak_dec_timestamp_step -------------------------------------------------------------------------------------------------
-struct TsParams {
-  GsParams g;
-  int32_t* ts_last;
+  int32_t* ts_last;  // (this line and the next: read with TS only)
   int ts_begin, no_timestamps_id, max_initial;
 };
 
-template <bool VEC>
-__global__ __launch_bounds__(GS_THREADS) void dec_timestamp_kernel(const TsParams q) {
+template <bool VEC, bool TS>
+__global__ __launch_bounds__(GS_THREADS) void dec_token_step_kernel(const GsParams p) {
   __shared__ float red[16];
   __shared__ int32_t ired[16];
-  const GsParams& p = q.g;
   const int tid = threadIdx.x, row = blockIdx.x;
   const float* x = p.logits + (long)row * p.ldv;
-  const uint8_t* const s0 = p.suppress;
-  const uint8_t* const s1 = p.begin_suppress;
   const bool was_finished = p.finished[row] != 0;  // (read by every thread before thread 0 writes it, behind the barriers below)
   int token = p.pad_id;
   float logprob = 0.f;
   int ts_new = -1;  // what ts_last[row] becomes; only an unfinished row writes it
   if (!was_finished) {  // (uniform over the workgroup)
-    const int V = p.V, n = p.t, tsb = q.ts_begin;
-    const int32_t* const hist = p.tokens + (long)row * p.ldt;
-    const int ts_prev = n == 0 ? -1 : q.ts_last[row];  // (every thread reads it before thread 0 writes it, behind the barriers below)
-    ts_new = ts_prev;
-    const TsRules rules = ts_rules(hist, n, ts_prev, V, tsb, p.eos_id, q.no_timestamps_id, q.max_initial);
-    const auto allowed = [&](int c) { return rules.allowed(c); };
-
-    const int n4 = VEC ? (V & ~3) : 0;
-    float mt = -INFINITY, ms = -INFINITY;  // the text maximum, the timestamp maximum
+    const int V = p.V, tsb = TS ? p.ts_begin : V;  // without TS every column is a text column and none is tested
+    if constexpr (TS) ts_new = p.t == 0 ? -1 : p.ts_last[row];  // (every thread reads it before thread 0 writes it, behind the barriers below)
+    const auto rules = [&] {
+      if constexpr (TS)
+        return ts_rules(p.tokens + (long)row * p.ldt, p.t, ts_new, V, tsb, p.eos_id, p.no_timestamps_id, p.max_initial);
+      else
+        return NoRules{};
+    }();
+    // pass one: the text and the timestamp maximum, each with its lowest column (ms, is, ss keep their initial values without TS)
+    float mt = -INFINITY, ms = -INFINITY;
     int32_t it = INT_MAX, is = INT_MAX;
-    for (int i = tid * 4; i < n4; i += GS_THREADS * 4) {
-      const float4 f = *reinterpret_cast<const float4*>(x + i);
-      uint32_t mk = s0 ? *reinterpret_cast<const uint32_t*>(s0 + i) : 0u;
-      if (s1) mk |= *reinterpret_cast<const uint32_t*>(s1 + i);
-      const float v[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int c = i + e;
-        if (((mk >> (8 * e)) & 0xffu) || !allowed(c)) continue;
-        if (c < tsb) {
-          if (v[e] > mt) mt = v[e], it = c;  // strict: within a thread's increasing columns the first maximum stays
-        } else if (v[e] > ms) {
-          ms = v[e], is = c;
-        }
-      }
-    }
-    for (int i = n4 + tid; i < V; i += GS_THREADS) {
-      const bool sup = (s0 && s0[i]) || (s1 && s1[i]);
-      const float v = x[i];
-      if (sup || !allowed(i)) continue;
-      if (i < tsb) {
-        if (v > mt || (v == mt && i < it)) mt = v, it = i;
-      } else if (v > ms || (v == ms && i < is)) {
-        ms = v, is = i;
-      }
-    }
+    scan_allowed<VEC>(x, p.suppress, p.begin_suppress, V, rules, [&](int c, float v) {
+      // strict: within a thread's increasing columns the first maximum stays.  (Selects, not `if text .. else ..` around two
+      // like updates: the compiler merged those into one update through a selected pointer, which put the four in scratch.)
+      const bool text = !TS || c < tsb, bt = text && v > mt, bs = !text && v > ms;
+      mt = bt ? v : mt, it = bt ? c : it;
+      if constexpr (TS) ms = bs ? v : ms, is = bs ? c : is;
+    });
     block_argmax(mt, it, red, ired);
-    block_argmax(ms, is, red, ired);
-    const float M = fmaxf(mt, ms);
+    if constexpr (TS) block_argmax(ms, is, red, ired);
     if (it < V || is < V) {  // (a row with no allowed column, the caller's error, emits pad_id with log-prob 0)
-      float st = 0.f, ss = 0.f;  // sums of exp(x - M) over the allowed text / timestamp columns
-      for (int i = tid * 4; i < n4; i += GS_THREADS * 4) {
-        const float4 f = *reinterpret_cast<const float4*>(x + i);
-        uint32_t mk = s0 ? *reinterpret_cast<const uint32_t*>(s0 + i) : 0u;
-        if (s1) mk |= *reinterpret_cast<const uint32_t*>(s1 + i);
-        const float v[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int c = i + e;
-          const float ex = (((mk >> (8 * e)) & 0xffu) || !allowed(c)) ? 0.f : expf(v[e] - M);
-          st += c < tsb ? ex : 0.f;
-          ss += c < tsb ? 0.f : ex;
-        }
-      }
-      for (int i = n4 + tid; i < V; i += GS_THREADS) {
-        const bool sup = (s0 && s0[i]) || (s1 && s1[i]);
-        const float ex = (sup || !allowed(i)) ? 0.f : expf(x[i] - M);
-        st += i < tsb ? ex : 0.f;
-        ss += i < tsb ? 0.f : ex;
-      }
+      const float M = TS ? fmaxf(mt, ms) : mt;
+      float st = 0.f, ss = 0.f;  // pass two: sums of exp(x - M) over the allowed text / timestamp columns, in column order
+      scan_allowed<VEC>(x, p.suppress, p.begin_suppress, V, rules, [&](int c, float v) {
+        const float ex = expf(v - M);
+        st += (!TS || c < tsb) ? ex : 0.f;
+        if constexpr (TS) ss += c < tsb ? 0.f : ex;
+      });
       st = block_sum(st, red);
-      ss = block_sum(ss, red);
-      // the timestamps' mass against the likeliest text token: log S_ts - log S > m_text - M - log S
-      if (ts_mass_wins(ss, mt, M)) {
+      if constexpr (TS) ss = block_sum(ss, red);
+      if (TS && ts_mass_wins(ss, mt, M)) {
         token = is;
         logprob = (ms - M) - logf(ss);
       } else {
         token = (it < V && mt >= ms) ? it : is;  // (text ids lie below the timestamps: the lowest id on a tie)
-        logprob = -logf(st + ss);                // x[token] = M
+        logprob = -logf(st + ss);                // x[token] = M; without TS ss is +0: -log of the one sum, to the bit
       }
-      if (token >= tsb) ts_new = token;
+      if (TS && token >= tsb) ts_new = token;
     }
   }
   if (tid == 0) {
@@ -400,7 +268,7 @@ __global__ __launch_bounds__(GS_THREADS) void dec_timestamp_kernel(const TsParam
     p.logprobs[(long)row * p.ldt + p.t] = logprob;
     const bool now_finished = was_finished || token == p.eos_id;
     p.finished[row] = now_finished ? 1 : 0;
-    if (!was_finished) q.ts_last[row] = ts_new;
+    if (TS && !was_finished) p.ts_last[row] = ts_new;
     if (!now_finished) atomicAdd(p.n_unfinished, 1);  // (an integer count on the word the entry zeroed: order-free)
   }
   if (p.h_next) form_h_next(p.h_next + (long)row * p.D, p.embed_tokens, p.embed_positions, token, p.V, p.D, p.next_pos);
@@ -473,21 +341,26 @@ int greedy_params(const char* who, const float* logits, long ldv, int B, int V, 
   SSAK_REQUIRE(B > 0 && V > 0 && ldv >= V, "%s: bad shape B=%d V=%d ldv=%ld", who, B, V, ldv);
   SSAK_REQUIRE(eos_id >= 0 && eos_id < V && pad_id >= 0 && pad_id < V, "%s: eos_id=%d / pad_id=%d outside [0, %d)", who, eos_id, pad_id, V);
   SSAK_REQUIRE(t >= 0 && t < ldt, "%s: step t=%d outside the token buffer's %ld columns", who, t, ldt);
-  if (h_next) {
-    SSAK_REQUIRE(embed_tokens && embed_positions, "%s: h_next needs the two embedding tables", who);
-    SSAK_REQUIRE(D > 0 && D % 8 == 0 && max_positions > 0, "%s: bad shape D=%d max_positions=%d", who, D, max_positions);
-    SSAK_REQUIRE(next_pos >= 0 && next_pos < max_positions, "%s: next_pos=%d overruns the position table of %d", who, next_pos, max_positions);
-    SSAK_REQUIRE(aligned16(embed_tokens) && aligned16(embed_positions) && aligned16(h_next), "%s: a buffer is not 16-byte aligned", who);
-  }
+  if (const int rc = check_h_next(who, embed_tokens, embed_positions, D, max_positions, next_pos, h_next)) return rc;
   GsParams& p = *out;
   p.logits = logits, p.suppress = suppress, p.begin_suppress = first ? begin_suppress : nullptr;
   p.embed_tokens = (const bf16*)embed_tokens, p.embed_positions = (const bf16*)embed_positions;
   p.finished = finished, p.n_unfinished = n_unfinished, p.tokens = tokens, p.logprobs = logprobs, p.h_next = (bf16*)h_next;
   p.ldv = ldv, p.ldt = ldt, p.V = V, p.D = D, p.t = t, p.next_pos = next_pos, p.eos_id = eos_id, p.pad_id = pad_id;
+  p.ts_last = nullptr, p.ts_begin = p.no_timestamps_id = 0, p.max_initial = -1;
   return SSAK_OK;
 }
-bool greedy_vec(const GsParams& p) {
-  return aligned16(p.logits) && p.ldv % 4 == 0 && ((uintptr_t)p.suppress & 3) == 0 && ((uintptr_t)p.begin_suppress & 3) == 0;
+// the count zeroed, then the one kernel on B rows
+template <bool TS>
+int launch_token_step(const GsParams& p, int B, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  SSAK_HIP(hipMemsetAsync(p.n_unfinished, 0, sizeof(int32_t), st));
+  if (scan_vec(p.logits, p.ldv, p.suppress, p.begin_suppress))
+    dec_token_step_kernel<true, TS><<<B, GS_THREADS, 0, st>>>(p);
+  else
+    dec_token_step_kernel<false, TS><<<B, GS_THREADS, 0, st>>>(p);
+  SSAK_LAUNCH_CHECK();
+  return SSAK_OK;
 }
 }  // namespace
 
@@ -498,15 +371,7 @@ extern "C" int ssak_dec_greedy_step(const float* logits, long ldv, int B, int V,
   GsParams p;
   const int rc = greedy_params("dec_greedy_step", logits, ldv, B, V, suppress, begin_suppress, first, embed_tokens, embed_positions, D, max_positions,
                                next_pos, eos_id, pad_id, finished, n_unfinished, tokens, logprobs, ldt, t, h_next, &p);
-  if (rc != SSAK_OK) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  SSAK_HIP(hipMemsetAsync(n_unfinished, 0, sizeof(int32_t), st));
-  if (greedy_vec(p))
-    dec_greedy_kernel<true><<<B, GS_THREADS, 0, st>>>(p);
-  else
-    dec_greedy_kernel<false><<<B, GS_THREADS, 0, st>>>(p);
-  SSAK_LAUNCH_CHECK();
-  return SSAK_OK;
+  return rc != SSAK_OK ? rc : launch_token_step<false>(p, B, stream);
 }
 
 extern "C" int ssak_dec_timestamp_step(const float* logits, long ldv, int B, int V, const uint8_t* suppress, const uint8_t* begin_suppress,
@@ -514,20 +379,13 @@ extern "C" int ssak_dec_timestamp_step(const float* logits, long ldv, int B, int
                                        const void* embed_positions, int D, int max_positions, int next_pos, int eos_id, int pad_id,
                                        uint8_t* finished, int32_t* n_unfinished, int32_t* tokens, float* logprobs, long ldt, int t,
                                        int32_t* ts_last, void* h_next, void* stream) {
-  TsParams q;
+  GsParams p;
   const int rc = greedy_params("dec_timestamp_step", logits, ldv, B, V, suppress, begin_suppress, first, embed_tokens, embed_positions, D,
-                               max_positions, next_pos, eos_id, pad_id, finished, n_unfinished, tokens, logprobs, ldt, t, h_next, &q.g);
+                               max_positions, next_pos, eos_id, pad_id, finished, n_unfinished, tokens, logprobs, ldt, t, h_next, &p);
   if (rc != SSAK_OK) return rc;
   SSAK_REQUIRE(ts_last, "dec_timestamp_step: ts_last is NULL");
   SSAK_REQUIRE(ts_begin > eos_id && ts_begin < V, "dec_timestamp_step: ts_begin=%d must lie in (eos_id=%d, V=%d)", ts_begin, eos_id, V);
   SSAK_REQUIRE(no_timestamps_id >= 0 && no_timestamps_id < V, "dec_timestamp_step: no_timestamps_id=%d outside [0, %d)", no_timestamps_id, V);
-  q.ts_last = ts_last, q.ts_begin = ts_begin, q.no_timestamps_id = no_timestamps_id, q.max_initial = max_initial < 0 ? -1 : max_initial;
-  const hipStream_t st = (hipStream_t)stream;
-  SSAK_HIP(hipMemsetAsync(n_unfinished, 0, sizeof(int32_t), st));
-  if (greedy_vec(q.g))
-    dec_timestamp_kernel<true><<<B, GS_THREADS, 0, st>>>(q);
-  else
-    dec_timestamp_kernel<false><<<B, GS_THREADS, 0, st>>>(q);
-  SSAK_LAUNCH_CHECK();
-  return SSAK_OK;
+  p.ts_last = ts_last, p.ts_begin = ts_begin, p.no_timestamps_id = no_timestamps_id, p.max_initial = max_initial < 0 ? -1 : max_initial;
+  return launch_token_step<true>(p, B, stream);
 }

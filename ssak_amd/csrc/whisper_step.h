@@ -1,6 +1,7 @@
-// What the token-selection kernels of the Whisper generation loop share (whisper_generate.hip: dec_timestamp_kernel; whisper_beam.hip:
-// dec_beam_topk_kernel): the column predicate of whisper's ApplyTimestampRules, its mass rule, and the workgroup arg-max.  One
-// statement of the rules, so that the beam's candidates are filtered exactly as the greedy token is.
+// What the token-selection kernels of the Whisper generation loop share (whisper_generate.hip: dec_token_step_kernel; whisper_beam.hip:
+// dec_beam_topk_kernel): the column predicate of whisper's ApplyTimestampRules, the masked scan of a logits row, its mass rule, the
+// workgroup arg-max, the next input row, and the host checks the two files' entries have in common.  One statement of each, so that
+// the beam's candidates are filtered, reduced and scored exactly as the greedy token is.
 #pragma once
 #include <limits.h>
 
@@ -31,6 +32,34 @@ __device__ __forceinline__ TsRules ts_rules(const int32_t* hist, int n, int ts_p
 
 // no rules: every column is a text column (the greedy step's predicate is the suppress masks alone)
 __device__ __forceinline__ TsRules no_rules(int V) { return TsRules{V, 0, V, -1, -1}; }
+// the same as a type: a kernel instantiated on it carries no per-column test
+struct NoRules {
+  __device__ __forceinline__ bool allowed(int) const { return true; }
+};
+
+// f(column, value) on every column of the row that no mask byte hits and the rules allow; a thread's columns come in increasing order
+template <bool VEC, typename R, typename F>
+__device__ __forceinline__ void scan_allowed(const float* x, const uint8_t* s0, const uint8_t* s1, int V, const R& rules, F f) {
+  const int tid = threadIdx.x;
+  const int n4 = VEC ? (V & ~3) : 0;
+  for (int i = tid * 4; i < n4; i += GS_THREADS * 4) {
+    const float4 q = *reinterpret_cast<const float4*>(x + i);
+    uint32_t mk = s0 ? *reinterpret_cast<const uint32_t*>(s0 + i) : 0u;
+    if (s1) mk |= *reinterpret_cast<const uint32_t*>(s1 + i);
+    const float v[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (!((mk >> (8 * e)) & 0xffu) && rules.allowed(i + e)) f(i + e, v[e]);
+  }
+  for (int i = n4 + tid; i < V; i += GS_THREADS) {
+    const bool sup = (s0 && s0[i]) || (s1 && s1[i]);
+    if (!sup && rules.allowed(i)) f(i, x[i]);
+  }
+}
+// whether scan_allowed may take its vector loop: 16-byte logits rows, 4-byte mask words
+inline bool scan_vec(const float* logits, long ldv, const uint8_t* s0, const uint8_t* s1) {
+  return aligned16(logits) && ldv % 4 == 0 && ((uintptr_t)s0 & 3) == 0 && ((uintptr_t)s1 & 3) == 0;
+}
 
 // the timestamps' mass against the likeliest text token: log S_ts - log S > m_text - M - log S, with ss = S_ts / exp(M)
 __device__ __forceinline__ bool ts_mass_wins(float ss, float mt, float M) { return ss > 0.f && logf(ss) > mt - M; }
@@ -75,4 +104,14 @@ __device__ __forceinline__ void form_h_next(bf16* h_row, const bf16* embed_token
     for (int k = 0; k < 8; ++k) e[k] += r[k];
     st8<bf16>(h_row + ch * 8, f_to_chunk8<bf16>(e));
   }
+}
+// what an entry that forms h_next refuses (`who`: the entry's name in the message)
+inline int check_h_next(const char* who, const void* embed_tokens, const void* embed_positions, int D, int max_positions, int next_pos,
+                        const void* h_next) {
+  if (!h_next) return SSAK_OK;
+  SSAK_REQUIRE(embed_tokens && embed_positions, "%s: h_next needs the two embedding tables", who);
+  SSAK_REQUIRE(D > 0 && D % 8 == 0 && max_positions > 0, "%s: bad shape D=%d max_positions=%d", who, D, max_positions);
+  SSAK_REQUIRE(next_pos >= 0 && next_pos < max_positions, "%s: next_pos=%d overruns the position table of %d", who, next_pos, max_positions);
+  SSAK_REQUIRE(aligned16(embed_tokens) && aligned16(embed_positions) && aligned16(h_next), "%s: a buffer is not 16-byte aligned", who);
+  return SSAK_OK;
 }

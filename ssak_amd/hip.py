@@ -787,27 +787,46 @@ def dec_attention_step(q, k, v, n_keys: int, nh: int, *, klens=None, n_split: in
     return ctx
 
 
+def _assert_masks(V: int, *masks):
+    for m in masks:
+        assert m is None or (m.is_cuda and m.dtype == torch.uint8 and m.numel() == V and m.is_contiguous())
+
+
+def _h_next_dims(embed_tokens, embed_positions, h_next, rows: int):
+    """(D, max_positions) of the tables behind ``h_next`` [rows, D] bf16; (0, 0) when no ``h_next`` is formed."""
+    if h_next is None:
+        return 0, 0
+    assert embed_tokens.dtype == torch.bfloat16 and embed_tokens.is_contiguous() and embed_positions.is_contiguous()
+    D, max_pos = embed_tokens.shape[1], embed_positions.shape[0]
+    assert h_next.dtype == torch.bfloat16 and h_next.is_contiguous() and tuple(h_next.shape) == (rows, D)
+    return D, max_pos
+
+
+def _token_step_args(logits, V, finished, n_unfinished, tokens, logprobs, t, eos_id, pad_id, suppress, begin_suppress, first, embed_tokens,
+                     embed_positions, next_pos, h_next):
+    """What :func:`dec_greedy_step` and :func:`dec_timestamp_step` check and pass alike -> the entries' leading arguments (logits ..
+    first) and the run from the embedding tables to ``t``."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    B = logits.shape[0]
+    assert tokens.dtype == torch.int32 and logprobs.dtype == torch.float32 and tokens.shape == logprobs.shape and tokens.shape[0] == B
+    assert tokens.is_contiguous() and logprobs.is_contiguous()
+    assert finished.dtype == torch.uint8 and finished.numel() == B and n_unfinished.dtype == torch.int32
+    _assert_masks(V, suppress, begin_suppress)
+    D, max_pos = _h_next_dims(embed_tokens, embed_positions, h_next, B)
+    return ((ptr(logits), logits.stride(0), B, int(V), ptr(suppress), ptr(begin_suppress), int(bool(first))),
+            (ptr(embed_tokens), ptr(embed_positions), D, max_pos, int(next_pos), int(eos_id), int(pad_id), ptr(finished), ptr(n_unfinished),
+             ptr(tokens), ptr(logprobs), tokens.shape[1], int(t)))
+
+
 def dec_greedy_step(logits, V: int, *, finished, n_unfinished, tokens, logprobs, t: int, eos_id: int, pad_id: int, suppress=None,
                     begin_suppress=None, first: bool = False, embed_tokens=None, embed_positions=None, next_pos: int = 0, h_next=None):
     """``ssak_dec_greedy_step`` on logits [B, ldv] fp32: writes ``tokens[:, t]`` (int32 [B, ldt]), ``logprobs[:, t]`` (fp32, same
     shape), ``finished`` (uint8 [B], read and written), ``n_unfinished`` (int32 [1]) and, when ``h_next`` [B, D] bf16 is given,
     the next step's input row ``embed_tokens[token] + embed_positions[next_pos]``.  ``suppress`` / ``begin_suppress``: uint8 [V]
     device masks.  Everything stays on the device."""
-    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
-    B = logits.shape[0]
-    assert tokens.dtype == torch.int32 and logprobs.dtype == torch.float32 and tokens.shape == logprobs.shape and tokens.shape[0] == B
-    assert tokens.is_contiguous() and logprobs.is_contiguous()
-    assert finished.dtype == torch.uint8 and finished.numel() == B and n_unfinished.dtype == torch.int32
-    for m in (suppress, begin_suppress):
-        assert m is None or (m.is_cuda and m.dtype == torch.uint8 and m.numel() == V and m.is_contiguous())
-    D = max_pos = 0
-    if h_next is not None:
-        assert embed_tokens.dtype == torch.bfloat16 and embed_tokens.is_contiguous() and embed_positions.is_contiguous()
-        D, max_pos = embed_tokens.shape[1], embed_positions.shape[0]
-        assert h_next.dtype == torch.bfloat16 and h_next.is_contiguous() and tuple(h_next.shape) == (B, D)
-    check(lib.ssak_dec_greedy_step(ptr(logits), logits.stride(0), B, int(V), ptr(suppress), ptr(begin_suppress), int(bool(first)),
-                                   ptr(embed_tokens), ptr(embed_positions), D, max_pos, int(next_pos), int(eos_id), int(pad_id), ptr(finished),
-                                   ptr(n_unfinished), ptr(tokens), ptr(logprobs), tokens.shape[1], int(t), ptr(h_next), stream()))
+    head, mid = _token_step_args(logits, V, finished, n_unfinished, tokens, logprobs, t, eos_id, pad_id, suppress, begin_suppress, first,
+                                 embed_tokens, embed_positions, next_pos, h_next)
+    check(lib.ssak_dec_greedy_step(*head, *mid, ptr(h_next), stream()))
 
 
 def dec_timestamp_step(logits, V: int, *, finished, n_unfinished, tokens, logprobs, t: int, eos_id: int, pad_id: int, ts_begin: int,
@@ -816,23 +835,10 @@ def dec_timestamp_step(logits, V: int, *, finished, n_unfinished, tokens, logpro
     """``ssak_dec_timestamp_step`` (ABI 620): :func:`dec_greedy_step` under whisper's timestamp rules.  ``ts_last``: int32 [B] on the
     device, the row's most recent timestamp id or -1 (written at ``t == 0``, read and updated afterwards); ``max_initial``: the
     largest index of the first timestamp, -1 for none.  The history is what the kernel wrote at ``tokens[:, :t]``."""
-    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
-    B = logits.shape[0]
-    assert tokens.dtype == torch.int32 and logprobs.dtype == torch.float32 and tokens.shape == logprobs.shape and tokens.shape[0] == B
-    assert tokens.is_contiguous() and logprobs.is_contiguous()
-    assert finished.dtype == torch.uint8 and finished.numel() == B and n_unfinished.dtype == torch.int32
-    assert ts_last is None or (ts_last.is_cuda and ts_last.dtype == torch.int32 and ts_last.numel() == B and ts_last.is_contiguous())
-    for m in (suppress, begin_suppress):
-        assert m is None or (m.is_cuda and m.dtype == torch.uint8 and m.numel() == V and m.is_contiguous())
-    D = max_pos = 0
-    if h_next is not None:
-        assert embed_tokens.dtype == torch.bfloat16 and embed_tokens.is_contiguous() and embed_positions.is_contiguous()
-        D, max_pos = embed_tokens.shape[1], embed_positions.shape[0]
-        assert h_next.dtype == torch.bfloat16 and h_next.is_contiguous() and tuple(h_next.shape) == (B, D)
-    check(lib.ssak_dec_timestamp_step(ptr(logits), logits.stride(0), B, int(V), ptr(suppress), ptr(begin_suppress), int(bool(first)),
-                                      int(ts_begin), int(no_timestamps_id), int(max_initial), ptr(embed_tokens), ptr(embed_positions), D,
-                                      max_pos, int(next_pos), int(eos_id), int(pad_id), ptr(finished), ptr(n_unfinished), ptr(tokens),
-                                      ptr(logprobs), tokens.shape[1], int(t), ptr(ts_last), ptr(h_next), stream()))
+    head, mid = _token_step_args(logits, V, finished, n_unfinished, tokens, logprobs, t, eos_id, pad_id, suppress, begin_suppress, first,
+                                 embed_tokens, embed_positions, next_pos, h_next)
+    assert ts_last is None or (ts_last.is_cuda and ts_last.dtype == torch.int32 and ts_last.numel() == logits.shape[0] and ts_last.is_contiguous())
+    check(lib.ssak_dec_timestamp_step(*head, int(ts_begin), int(no_timestamps_id), int(max_initial), *mid, ptr(ts_last), ptr(h_next), stream()))
 
 
 # ------------------------------------------------------------------ Whisper beam search (ABI 630): nb hypotheses per audio, R = B * nb rows
@@ -869,8 +875,7 @@ def dec_beam_topk(logits, V: int, nb: int, *, done, cand_token, cand_logprob, eo
     assert done.dtype == torch.uint8 and done.numel() == B and done.is_contiguous()
     assert cand_token.dtype == torch.int32 and cand_logprob.dtype == torch.float32 and cand_token.shape == cand_logprob.shape
     assert cand_token.dim() == 2 and cand_token.shape[0] == R and cand_token.is_contiguous() and cand_logprob.is_contiguous()
-    for m in (suppress, begin_suppress):
-        assert m is None or (m.is_cuda and m.dtype == torch.uint8 and m.numel() == V and m.is_contiguous())
+    _assert_masks(V, suppress, begin_suppress)
     ldt = 0
     if tokens is not None:
         assert tokens.dtype == torch.int32 and tokens.is_contiguous() and tokens.shape[0] == R
@@ -905,11 +910,7 @@ def dec_beam_select(cand_token, cand_logprob, nb: int, V: int, *, sum_logprob, s
     assert n_fin.dtype == torch.int32 and n_fin.numel() == B and done.dtype == torch.uint8 and done.numel() == B
     assert n_unfinished.dtype == torch.int32
     assert ts_last is None or (ts_last.dtype == torch.int32 and ts_last.numel() == R and ts_last.is_contiguous())
-    D = max_pos = 0
-    if h_next is not None:
-        assert embed_tokens.dtype == torch.bfloat16 and embed_tokens.is_contiguous() and embed_positions.is_contiguous()
-        D, max_pos = embed_tokens.shape[1], embed_positions.shape[0]
-        assert h_next.dtype == torch.bfloat16 and h_next.is_contiguous() and tuple(h_next.shape) == (R, D)
+    D, max_pos = _h_next_dims(embed_tokens, embed_positions, h_next, R)
     check(lib.ssak_dec_beam_select(ptr(cand_token), ptr(cand_logprob), B, nb, cand_token.shape[1], int(V), ptr(sum_logprob), ptr(src), ptr(tokens),
                                    ptr(logprobs), ldt, int(t), ptr(ts_last), int(ts_begin), ptr(fin_tokens), ptr(fin_logprobs), ptr(fin_len),
                                    ptr(fin_sum), ptr(n_fin), ptr(done), ptr(n_unfinished), ptr(embed_tokens), ptr(embed_positions), D, max_pos,

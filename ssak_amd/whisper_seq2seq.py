@@ -25,6 +25,9 @@ utterance through the layers -- ``ssak_dec_attention_step`` on the cache and on 
 logits processors, the arg-max, the log-probability, the finished flags and the next input row.  The loop stays on the device:
 the host reads one pinned word every ``poll_every`` steps and the tokens once at the end.
 
+Greedy and beam search run the one loop :meth:`WhisperSeq2Seq._gen_loop` (select, poll the pinned word, step); they differ in the
+selection they pass it.  The two token-step entries launch one kernel, ``dec_token_step_kernel``, with and without the rules.
+
 With ``timestamps=True`` the step is ``ssak_dec_timestamp_step`` (whisper's ``ApplyTimestampRules`` on the device) and the call
 also returns ``no_speech_prob``; :meth:`WhisperSeq2Seq.transcribe` (ssak_amd/whisper_transcribe.py) seeks a 30 s window through
 files of any length by the timestamps it predicted, as ``model.transcribe`` does.
@@ -256,7 +259,9 @@ def _decoder_layout(cfg: WhisperSeq2SeqConfig):
 
 
 class WhisperSeq2Seq:
-    """``WhisperSeq2Seq.from_pretrained(folder)``; :meth:`encode`, :meth:`decode_logprobs`, :meth:`score`, :meth:`detect_language`."""
+    """``WhisperSeq2Seq.from_pretrained(folder)``; :meth:`encode`, :meth:`decode_logprobs`, :meth:`score`, :meth:`detect_language`,
+    :meth:`generate`, :meth:`transcribe`.  Two layer walks (:meth:`_decoder_hidden`, teacher-forced; :meth:`_gen_step`, one row on the
+    cache), one chunked vocabulary projection (:meth:`_project_chunks`) and one generation loop (:meth:`_gen_loop`)."""
 
     def __init__(self, config: WhisperSeq2SeqConfig, device: str = "cuda:0", seed: int = 69):
         if not torch.cuda.is_available():
@@ -449,6 +454,16 @@ class WhisperSeq2Seq:
         hip.gemm(x, self._w("embed_tokens.weight"), logits, n, Vp, D, lda=D, ldb=D, ldc=Vp)
         return logits
 
+    def _project_chunks(self, x: torch.Tensor):
+        """:meth:`_project` of ``x`` [R, D], ``min(row_chunk, R)`` rows at a time (the workspace is never larger than the call needs,
+        nor than ``row_chunk`` rows) -> per chunk (first row, rows, logits).  Every chunk's logits sit in the one workspace: the
+        consumer enqueues its reads before it asks for the next."""
+        R = x.shape[0]
+        chunk = min(self.row_chunk, R)
+        for r0 in range(0, R, chunk):
+            n = min(chunk, R - r0)
+            yield r0, n, self._project(x[r0:r0 + n], chunk)
+
     @staticmethod
     def _tokens(tokens, lens):
         t = tokens.detach().cpu().numpy() if torch.is_tensor(tokens) else np.asarray(tokens)
@@ -469,10 +484,8 @@ class WhisperSeq2Seq:
         x = self._decoder_hidden(enc, t, enc_lens)
         with torch.cuda.device(self.device):
             full = torch.empty((x.shape[0], self._w("embed_tokens.weight").shape[0]), dtype=torch.float32, device=self.device)
-            chunk = min(self.row_chunk, x.shape[0])
-            for r0 in range(0, x.shape[0], chunk):
-                n = min(chunk, x.shape[0] - r0)
-                full[r0:r0 + n].copy_(self._project(x[r0:r0 + n], chunk))
+            for r0, n, logits in self._project_chunks(x):
+                full[r0:r0 + n].copy_(logits)
         return full.view(t.shape[0], t.shape[1], -1)[:, :, :self.config.vocab_size]
 
     def decode_logprobs(self, enc, tokens, lens=None, enc_lens=None) -> torch.Tensor:
@@ -486,14 +499,9 @@ class WhisperSeq2Seq:
         for b in range(B):
             targets[b, :lens[b] - 1] = t[b, 1:lens[b]]
         targets = targets.reshape(-1)
-        V, R = self.config.vocab_size, B * L
-        parts = []
+        V = self.config.vocab_size
         with torch.cuda.device(self.device):
-            chunk = min(self.row_chunk, R)  # (the workspace is never larger than the call needs, nor than ROW_CHUNK rows)
-            for r0 in range(0, R, chunk):
-                n = min(chunk, R - r0)
-                logits = self._project(x[r0:r0 + n], chunk)
-                parts.append(hip.token_logprobs(logits, V, targets[r0:r0 + n])[1])
+            parts = [hip.token_logprobs(logits, V, targets[r0:r0 + n])[1] for r0, n, logits in self._project_chunks(x)]
             lp = parts[0] if len(parts) == 1 else torch.cat(parts)
         return lp.view(B, L)[:, :L - 1]
 
@@ -522,12 +530,7 @@ class WhisperSeq2Seq:
         sot = np.full((B, 1), self.config.decoder_start_token_id, dtype=np.int64)
         x = self._decoder_hidden(enc, sot, enc_lens, cross_kv=cross_kv)
         with torch.cuda.device(self.device):
-            parts = []
-            chunk = min(self.row_chunk, B)
-            for r0 in range(0, B, chunk):
-                n = min(chunk, B - r0)
-                logits = self._project(x[r0:r0 + n], chunk)
-                parts.append(hip.token_logprobs(logits, self.config.vocab_size, None, self.lang_ids)[2:])
+            parts = [hip.token_logprobs(logits, self.config.vocab_size, None, self.lang_ids)[2:] for _, _, logits in self._project_chunks(x)]
             argmax = torch.cat([p[0] for p in parts])
             probs = torch.cat([p[1] for p in parts])
         by_id = {int(i): c for i, c in zip(self.lang_ids, self.lang_codes)}
@@ -601,14 +604,14 @@ class WhisperSeq2Seq:
             kv = st.self_kv.view(st.self_kv.shape[0], B, st.group, st.cap, 2 * st.D)
             kv[:, :, 1:, :P].copy_(kv[:, :, :1, :P].expand(-1, -1, st.group - 1, -1, -1))
         st.t = P
+        row = lambda i: self._project(x.view(B, P, st.D)[:, i].contiguous(), B)
         with torch.cuda.device(self.device):
             if also_row is None:
-                return self._project(x.view(B, P, st.D)[:, P - 1].contiguous(), B)
+                return row(P - 1)
             if not 0 <= also_row < P:
                 raise ValueError(f"also_row {also_row} outside the prompt's {P} positions")
-            side = self._project(x.view(B, P, st.D)[:, also_row].contiguous(), B)
-            lp = hip.token_logprobs(side, self.config.vocab_size, np.full(B, int(also_target), dtype=np.int32))[1]
-            return self._project(x.view(B, P, st.D)[:, P - 1].contiguous(), B), lp
+            lp = hip.token_logprobs(row(also_row), self.config.vocab_size, np.full(B, int(also_target), dtype=np.int32))[1]
+            return row(P - 1), lp
 
     def _gen_attend(self, st: _GenState, kind: str, q, kv, n_keys: int):
         """ctx [B, D] of the one new row: ``kv`` [B, rows, 2 D] is a layer's cache (``kind`` "self": the first ``n_keys`` rows
@@ -696,6 +699,24 @@ class WhisperSeq2Seq:
                 hip.dec_kv_reorder(st.self_kv, bs.src, bs.nb, bs.P, st.t)
         bs.i = i + 1
 
+    def _gen_loop(self, st: _GenState, logits: torch.Tensor, n_max: int, poll_every: int, select, n_unf: torch.Tensor, h_next: torch.Tensor) -> int:
+        """The loop of :meth:`generate`, greedy and beam: ``select(logits, i, last)`` closes step ``i`` (the token step, or
+        :meth:`_beam_step`) and leaves the next input rows in ``h_next`` unless ``last``; every ``poll_every`` steps the host reads
+        ``n_unf`` through a pinned word and stops at 0; :meth:`_gen_step` gives the next logits -> the steps taken."""
+        word = torch.zeros(1, dtype=torch.int32).pin_memory()
+        for i in range(n_max):
+            last = i + 1 == n_max
+            select(logits, i, last)
+            if last:
+                break
+            if poll_every and (i + 1) % poll_every == 0:
+                word.copy_(n_unf, non_blocking=True)
+                torch.cuda.current_stream().synchronize()
+                if int(word[0]) == 0:
+                    break
+            logits = self._gen_step(st, h_next)
+        return i + 1
+
     def _generate_beam(self, st: _GenState, logits: torch.Tensor, P: int, n_max: int, eos: int, pad: int, sup, bsup, ts, poll_every: int,
                        length_penalty, no_speech) -> GenerateResult:
         """The loop of :meth:`generate` with ``beam_size``: lock step over B * nb rows, the host polls ``n_unfinished`` (audios that
@@ -703,20 +724,8 @@ class WhisperSeq2Seq:
         B, nb = st.B, st.group
         bs = self._beam_begin(st, P, n_max, eos, pad, sup, bsup, ts)
         with torch.cuda.device(self.device):
-            word = torch.zeros(1, dtype=torch.int32).pin_memory()
-            logits = logits.repeat_interleave(nb, dim=0)
-            for i in range(n_max):
-                last = i + 1 == n_max
-                self._beam_step(st, bs, logits, last=last)
-                if last:
-                    break
-                if poll_every and bs.i % poll_every == 0:
-                    word.copy_(bs.n_unf, non_blocking=True)
-                    torch.cuda.current_stream().synchronize()
-                    if int(word[0]) == 0:
-                        break
-                logits = self._gen_step(st, bs.h_next)
-            steps = bs.i
+            steps = self._gen_loop(st, logits.repeat_interleave(nb, dim=0), n_max, poll_every,
+                                   lambda logits, i, last: self._beam_step(st, bs, logits, last=last), bs.n_unf, bs.h_next)
             host = lambda x: x.cpu().numpy()
             tok, lp, sums = host(bs.tokens).reshape(B, nb, -1), host(bs.logprobs).reshape(B, nb, -1), host(bs.sums)
             ftok, flp, flen, fsum, nfin = host(bs.fin_tokens), host(bs.fin_logprobs), host(bs.fin_len), host(bs.fin_sum), host(bs.n_fin)
@@ -873,28 +882,16 @@ class WhisperSeq2Seq:
             logprobs = torch.zeros((B, n_max), dtype=torch.float32, device=self.device)
             finished = torch.zeros(B, dtype=torch.uint8, device=self.device)
             n_unf = torch.zeros(1, dtype=torch.int32, device=self.device)
-            word = torch.zeros(1, dtype=torch.int32).pin_memory()
             h_next = torch.empty((B, st.D), dtype=torch.bfloat16, device=self.device)
-            steps = 0
+            step, rules = hip.dec_greedy_step, {}
             if timestamps:
-                ts_last = torch.full((B,), -1, dtype=torch.int32, device=self.device)
-                select = lambda **kw: hip.dec_timestamp_step(logits, V, ts_begin=ts_begin, no_timestamps_id=cfg.no_timestamps_token_id,
-                                                             max_initial=max_initial, ts_last=ts_last, **kw)
-            else:
-                select = lambda **kw: hip.dec_greedy_step(logits, V, **kw)
-            for i in range(n_max):
-                last = i + 1 == n_max
-                select(finished=finished, n_unfinished=n_unf, tokens=tokens, logprobs=logprobs, t=i, eos_id=eos, pad_id=pad, suppress=sup,
-                       begin_suppress=bsup, first=i == 0, embed_tokens=E, embed_positions=Pz, next_pos=P + i, h_next=None if last else h_next)
-                steps = i + 1
-                if last:
-                    break
-                if poll_every and steps % poll_every == 0:
-                    word.copy_(n_unf, non_blocking=True)
-                    torch.cuda.current_stream().synchronize()
-                    if int(word[0]) == 0:
-                        break
-                logits = self._gen_step(st, h_next)
+                step = hip.dec_timestamp_step
+                rules = dict(ts_begin=ts_begin, no_timestamps_id=cfg.no_timestamps_token_id, max_initial=max_initial,
+                             ts_last=torch.full((B,), -1, dtype=torch.int32, device=self.device))
+            select = lambda logits, i, last: step(logits, V, finished=finished, n_unfinished=n_unf, tokens=tokens, logprobs=logprobs, t=i,
+                                                  eos_id=eos, pad_id=pad, suppress=sup, begin_suppress=bsup, first=i == 0, embed_tokens=E,
+                                                  embed_positions=Pz, next_pos=P + i, h_next=None if last else h_next, **rules)
+            steps = self._gen_loop(st, logits, n_max, poll_every, select, n_unf, h_next)
             tok = tokens[:, :steps].cpu().numpy()
             lp = logprobs[:, :steps].double().cpu().numpy()
             if no_speech is not None:

@@ -10,6 +10,8 @@ Bars (fixed before the first run).  u = 2^-24.
   (tests/test_gpu_whisper_generate.py) with x_t the candidate's logit: rel = (4 D + K + 6) u, D = max_c |x_c - M| over the columns
   the rules allow BEFORE the mass decision (the columns the kernel's sums run over; M their maximum), K = ceil(V / 256) + 10,
   bar = rel + 2 u (|log s| + |M| + |lse|) + 2 u (|x_t| + |logprob|), s = the final row's sum of exp(x - M).
+  The first candidate at nb = 1 against ssak_dec_greedy_step / ssak_dec_timestamp_step on the same buffers: token and fp32 log-prob
+  equal bit for bit (the kernels share the scan, the reductions and the log-prob arithmetic of whisper_step.h).
 * ssak_dec_beam_select: everything exact; the score is one fp32 add (np.float32 in the restatement).
 * ssak_dec_kv_reorder: gathered rows bit-exact, every other byte unchanged.  ssak_dec_attention_step_grouped: bit for bit.
 * The loop by hand: tokens, sources, finished lists exact; sums within (the row's log-prob bar + u |sum|).  A step is exempt only
@@ -242,6 +244,89 @@ def test_beam_topk_vocabulary_width(hip):
     assert ct[0, 0] == 1000 and ct[1, :3].tolist() == [Vw - 1, Vw - 2, Vw - 5]
     ct, _ = run_topk(hip, x, Vw, hists, 2, "V=51865 greedy mode", timestamps=False, tsb=tsb, nots=nots, eos=eos)
     assert ct[1, :3].tolist() == [Vw - 1, Vw - 2, Vw - 5] and ct[2, :2].tolist() == [7, Vw - 1]
+
+
+def step_and_top1(hip, x, hists, t, timestamps, ts_in=None, sup=(), bsup=(), max_initial=-1, ldt=8):
+    """ssak_dec_beam_topk at nb = 1, then the token step (ssak_dec_timestamp_step with ``timestamps``, else ssak_dec_greedy_step), on
+    the same device logits, masks, histories and ts_last; every row unfinished -> (the step's tokens [R] int32 and log-probs [R] fp32,
+    the top-K's first candidates, the same types), on the host."""
+    R = x.shape[0]
+    tokens = torch.full((R, ldt), -5, dtype=torch.int32)
+    for r, h in enumerate(hists):
+        assert len(h) == t
+        tokens[r, :t] = torch.tensor(h, dtype=torch.int32)
+    tokens = tokens.to(DEV)
+    lps = torch.full((R, ldt), 9.0, dtype=torch.float32, device=DEV)
+    ts_last = torch.tensor(ts_in if ts_in is not None else [-1] * R, dtype=torch.int32, device=DEV)
+    ct = torch.full((R, 2), 77, dtype=torch.int32, device=DEV)
+    cl = torch.full((R, 2), 9.0, dtype=torch.float32, device=DEV)
+    masks = dict(suppress=mask_of(sup) if sup else None, begin_suppress=mask_of(bsup) if bsup else None, first=t == 0)
+    rules = dict(ts_begin=TSB, no_timestamps_id=NOTS, max_initial=max_initial, ts_last=ts_last) if timestamps else {}
+    hip.dec_beam_topk(x, V, 1, done=torch.zeros(R, dtype=torch.uint8, device=DEV), cand_token=ct, cand_logprob=cl, eos_id=EOS, t=t,
+                      timestamps=timestamps, tokens=tokens if timestamps else None, **masks, **rules)
+    step = hip.dec_timestamp_step if timestamps else hip.dec_greedy_step
+    step(x, V, finished=torch.zeros(R, dtype=torch.uint8, device=DEV), n_unfinished=torch.zeros(1, dtype=torch.int32, device=DEV), tokens=tokens,
+         logprobs=lps, t=t, eos_id=EOS, pad_id=PAD, **masks, **rules)
+    torch.cuda.synchronize()
+    return tokens[:, t].cpu(), lps[:, t].cpu(), ct[:, 0].cpu(), cl[:, 0].cpu()
+
+
+def test_token_step_is_the_top1_of_the_beam(hip):
+    """The greedy and the timestamp step against dec_beam_topk_kernel's first candidate at nb = 1, BIT FOR BIT (fp32 ``==``, no
+    tolerance): the two share the scan, the reduction and the log-probability arithmetic.  Six rows per launch of the planted
+    states above and of tests/test_gpu_whisper_timestamps.py, each on the vector path (128 columns) and on the scalar path (the
+    129-column view of a 131-column buffer)."""
+    g = base_rows(6, 51)  # greedy mode: suppressed / begin-suppressed maxima, an exact tie, eos, the last column
+    top = float(g[:, :V].max())
+    g[0, 50] = top + 5
+    g[1, 60] = top + 3
+    g[2, 17] = g[2, 90] = top + 1
+    g[3, EOS] = top + 2
+    g[5, V - 1] = top + 2
+    x0 = base_rows(6, 41)  # rules, t = 0, max_initial 5, both masks, junk in ts_last
+    x0[0, 17] = 12.0
+    x0[0, TSB + 2] = 6.0
+    x0[1, TSB + 9] = 12.0
+    x0[1, TSB + 5] = 6.0
+    x0[2, TSB + 1] = 12.0
+    x0[2, TSB + 3] = 9.0
+    x0[2, TSB + 0] = 6.0
+    x0[3, NOTS] = 12.0
+    x0[3, TSB + 4] = 6.0
+    x0[4, TSB + 1] = 12.0
+    x0[5, TSB + 4] = 6.0
+    x0[5, EOS] = 12.0
+    x1 = base_rows(6, 42)  # rules, t = 1, after [ts]: timestamps masked although they dominate; eos
+    x1[0, TSB + 6:V] = 12.0
+    x1[0, 33] = 6.0
+    x1[1, EOS] = 9.0
+    x2 = base_rows(6, 43)  # rules, t = 2, after [ts, text]: the mass rule won (row 0) and lost (row 1); <|notimestamps|>; an exact tie
+    x2[0, 40] = 8.0
+    x2[0, TSB:V] = 6.2
+    x2[0, TSB + 7] = 7.0
+    x2[0, TSB + 1] = 30.0
+    x2[1, 40] = 12.0
+    x2[2, NOTS] = 20.0
+    x2[2, 41] = 9.0
+    x2[3, TSB + 8] = x2[3, TSB + 12] = 9.0
+    cases = [("greedy first", g, [[]] * 6, 0, dict(timestamps=False, sup=[50, 120], bsup=[60, 3]), {0: None, 2: 17, 3: EOS, 5: V - 1}),
+             ("greedy not first", g, [[5, 6]] * 6, 2, dict(timestamps=False, sup=[50, 120], bsup=[60, 3]), {1: 60, 2: 17, 3: EOS}),
+             ("rules t=0", x0, [[]] * 6, 0, dict(timestamps=True, sup=[TSB + 1, 50], bsup=[TSB + 3, 60], max_initial=5, ts_in=[120, 121, 122, 123, 77, 125]),
+              {0: TSB + 2, 1: TSB + 5, 2: TSB, 3: TSB + 4, 5: TSB + 4}),
+             ("rules t=1", x1, [[TSB + 2]] * 6, 1, dict(timestamps=True, ts_in=[TSB + 2] * 6), {0: 33, 1: EOS}),
+             ("rules t=2", x2, [[TSB + 4, 7]] * 6, 2, dict(timestamps=True, ts_in=[TSB + 4] * 6), {0: TSB + 7, 1: 40, 2: 41, 3: TSB + 8})]
+    for name, x, hists, t, kw, planted in cases:
+        wide = torch.full((6, 131), 1e30)
+        wide[:, :V] = x[:, :V]
+        for path, xd in (("vector", x.to(DEV)), ("scalar", wide.to(DEV)[:, :129])):
+            tok, lp, ct, cl = step_and_top1(hip, xd, hists, t, **kw)
+            print(f"token step vs top-1, {name}, {path} path: tokens {tok.tolist()} / {ct.tolist()}, log-probs as int32 "
+                  f"{lp.view(torch.int32).tolist()} / {cl.view(torch.int32).tolist()}")
+            for r, want in planted.items():
+                assert want is None or int(tok[r]) == want, (name, path, r, int(tok[r]), want)
+            assert int(tok[0]) != 50 and bool(torch.isfinite(lp).all()) and bool((lp <= 0).all())
+            assert torch.equal(tok, ct), (name, path, "tokens")
+            assert bool((lp == cl).all()), (name, path, "log-probs: fp32 ==, no tolerance")
 
 
 # ------------------------------------------------------------------------------------------------------------ 2. select
