@@ -20,7 +20,7 @@ OBJS := $(patsubst $(CSRC)/%,$(OBJ)/%.o,$(SRCS))
 
 all: $(LIB)
 
-$(OBJ)/%.hip.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/gemm_common.h $(CSRC)/kernels.h $(CSRC)/whisper_step.h include/ssak_hip.h
+$(OBJ)/%.hip.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/gemm_common.h $(CSRC)/kernels.h $(CSRC)/whisper_step.h $(CSRC)/wgrad_schedule.h include/ssak_hip.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -21,11 +21,9 @@
 #include <string.h>
 
 #include "kernels.h"
+#include "wgrad_schedule.h"
 
 namespace {
-
-// buffer sets of the queued weight-gradient operands (three: a layer's last product may wait for the launch after next)
-constexpr int WGRAD_SETS = 3;
 
 struct PInfo {
   std::string name;
@@ -118,7 +116,7 @@ struct ssak_w2v2 {
   hipEvent_t params_ready = nullptr, stall_begin = nullptr, stall_end = nullptr;
   // per-handle execution options (ssak_w2v2_set_option)
   int dynamic_tiles = 0;
-  size_t xin[65] = {0};  // workspace offset of the INPUT of layer l (x[l]; a LayerDrop-skipped post-LN layer passes its input on: no copy)
+  size_t xin[SSAK_MAX_LAYERS + 1] = {0};  // workspace offset of the INPUT of layer l (x[l]; a LayerDrop-skipped post-LN layer passes its input on: no copy)
   int raw_input = 0;  // SSAK_W2V2_OPT_RAW_INPUT: input_values are raw full-length waveforms (group-norm feature encoder, frozen)
   int attn_bwd_mode = SSAK_ATTN_BWD_DEFAULT;
   int posconv_direct = 1;
@@ -147,6 +145,10 @@ struct ssak_w2v2 {
   const bf16* wt(int layer, int which) const {
     return (wtr_valid && keep[layer]) ? wtr + (size_t)layer * wtr_layer + wtr_off[which] : nullptr;
   }
+  // wqkv|wo|w1|w2 of one layer are contiguous: the layer's gradient range
+  long layer_span() const { return (lp[0].w2 + (long)cfg.hidden_size * cfg.intermediate_size) - lp[0].wqkv; }
+  // elements of the gradient buffer (the Whisper position table is fixed; a frozen feature encoder has no gradient)
+  long n_grad() const { return (cfg.arch == 1 || cfg.freeze_feature_encoder) ? n_train : n_total; }
 };
 
 namespace {
@@ -306,7 +308,7 @@ int check_config(const ssak_w2v2_config& c) {
     SSAK_REQUIRE(c.num_mel_bins > 0 && c.num_mel_bins % 8 == 0 && c.max_source_positions > 0, "whisper: num_mel_bins must be a multiple of 8");
     SSAK_REQUIRE(c.hidden_size % c.num_heads == 0 && (c.hidden_size / c.num_heads) % 8 == 0, "whisper: head_dim must be a multiple of 8");
     SSAK_REQUIRE(c.hidden_size % 8 == 0 && c.intermediate_size % 8 == 0 && c.vocab_size % 8 == 0, "whisper: d_model / ffn / vocab must be multiples of 8");
-    SSAK_REQUIRE(c.num_layers >= 1 && c.num_layers <= 64, "whisper: num_layers out of range");
+    SSAK_REQUIRE(c.num_layers >= 1 && c.num_layers <= SSAK_MAX_LAYERS, "whisper: num_layers out of range");
     return SSAK_OK;
   }
   SSAK_REQUIRE(c.arch == 0, "w2v2: arch must be 0 (wav2vec2) or 1 (whisper encoder)");
@@ -320,7 +322,7 @@ int check_config(const ssak_w2v2_config& c) {
   for (int i = 0; i < c.num_conv_layers; ++i) {
     SSAK_REQUIRE(c.conv_dim[i] % 8 == 0, "w2v2: conv_dim must be multiples of 8");
   }
-  SSAK_REQUIRE(c.num_layers >= 1 && c.num_layers <= 64, "w2v2: num_layers out of range");
+  SSAK_REQUIRE(c.num_layers >= 1 && c.num_layers <= SSAK_MAX_LAYERS, "w2v2: num_layers out of range");
   return SSAK_OK;
 }
 
@@ -589,75 +591,98 @@ struct GemmX : Gemm {
   GemmX(int M, int N, int K) : Gemm(M, N, K, EXACT) {}
 };
 
-// Weight-gradient products are not on the critical path of the backward: they are queued and launched together as ONE grouped
-// GEMM (ssak_gemm_bf16_grouped) instead of four launches per layer that each need split-K slabs and a reduction pass.  The
-// queue is packed greedily into launches of at most one round of 256 x 256 tiles (see flush_gemms in the backward): ~2.4 base
-// layers per launch (rounds 1-2: pairs of layers, 216 tiles, with the odd layer LayerDrop leaves over as four split-K
-// launches); under data parallelism a layer's gradient range is announced for the bucketed all-reduce as soon as its last
-// product has been launched.  All kept layers in one multi-round launch (1 188 tiles for eleven layers = 4.6 rounds) was
-// measured slower on one GPU: see the plan.
-struct WgradQueue {
-  static constexpr int CAP = 48;  // what ssak_gemm_bf16_grouped takes in one launch
-  ssak_gemm_desc d[CAP];
-  const void* A[CAP];
-  const void* B[CAP];
-  void* C[CAP];
-  int set[CAP];  // buffer set the product's operands live in
-  int n = 0, layers = 0, tiles = 0;
-  long pushed = 0, launched = 0;  // products ever queued / launched
-  bool f32 = false;
-  // gradient ranges to announce once the queued products have been launched, in LAYER ORDER: a data-parallel caller
-  // pairs the k-th announcement of every rank in one collective, and LayerDrop decisions differ between ranks, so a
-  // dropped layer's (zero) range must not overtake the kept layers still waiting here
-  long ann_off[64];
-  long ann_cnt[64];   // elements of the range (a layer's four matrices; the lm_head matrix)
-  long ann_last[64];  // the range's last product (sequence number), -1: nothing to wait for (a dropped layer)
-  int n_ann = 0;
-  static int tiles_of(const ssak_gemm_desc& g) { return ssak_cdiv(g.M, 256) * ssak_cdiv(g.N, 256); }
-  bool uses_set(int s) const {
-    for (int i = 0; i < n; ++i)
-      if (set[i] == s) return true;
-    return false;
-  }
-  void push(const Gemm& g, int buffer_set) {
-    set[n] = buffer_set;
-    ++pushed;
-    d[n] = g.d;
-    A[n] = g.A;
-    B[n] = g.B;
-    C[n] = g.C;
-    f32 = g.f32;
-    tiles += tiles_of(g.d);
-    ++n;
-  }
-  // launch what is queued: grouped when it fills at least 5/8 of a round of 256 workgroups, else one by one (split-K: the last,
-  // partial launch of a backward and tiny test models)
-  int flush(hipStream_t st, void* slab, size_t slab_bytes) {
-    int rc = SSAK_OK;
-    if (n > 0) {
-      if (f32) {
-        for (int i = 0; i < n && rc == SSAK_OK; ++i) rc = ssak_gemm_f32(&d[i], A[i], B[i], C[i], nullptr, nullptr, nullptr, (void*)st);
-      } else if (tiles >= 160) {
-        rc = ssak_gemm_bf16_grouped(d, n, A, B, C, (void*)st);
-      } else {
-        for (int i = 0; i < n && rc == SSAK_OK; ++i) {
-          d[i].split_k = 0;
-          rc = ssak_gemm_bf16(&d[i], A[i], B[i], C[i], nullptr, nullptr, nullptr, slab, slab_bytes, (void*)st);
-        }
-      }
-    }
-    launched += n;
-    n = 0;
-    tiles = 0;
-    return rc;
-  }
-};
-
 #define TRY(x)                    \
   do {                            \
     int rc__ = (x);               \
     if (rc__ != SSAK_OK) return rc__; \
   } while (0)
+
+// The engine's side of the weight-gradient schedule (wgrad_schedule.h: when products are launched and gradient ranges
+// announced): the queued products' descriptors and operands by slot, how a batch is launched, who hears of a finished range.
+struct WgradLaunch {
+  struct WgradQueue* q;
+  int operator()(int n, int tiles) const;
+};
+struct WgradAnnounce {
+  const ssak_w2v2* e;
+  void operator()(long off, long cnt) const {
+    if (e->on_ready && cnt > 0) e->on_ready(off, cnt, e->on_ready_user);
+  }
+};
+struct WgradQueue : WgradSchedule<WgradLaunch, WgradAnnounce> {
+  ssak_gemm_desc d[CAP];
+  const void* A[CAP];
+  const void* B[CAP];
+  void* C[CAP];
+  bool f32 = false;
+  const hipStream_t st;
+  void* const slab;
+  const size_t slab_bytes;
+  WgradQueue(const ssak_w2v2* e, hipStream_t st_, void* slab_, size_t slab_bytes_)
+      : WgradSchedule(WgradLaunch{this}, WgradAnnounce{e}), st(st_), slab(slab_), slab_bytes(slab_bytes_) {}
+  WgradQueue(const WgradQueue&) = delete;
+  int push(const Gemm& g, int buffer_set) {
+    int i;
+    TRY(WgradSchedule::push(ssak_cdiv(g.d.M, 256) * ssak_cdiv(g.d.N, 256), buffer_set, &i));
+    d[i] = g.d;
+    A[i] = g.A;
+    B[i] = g.B;
+    C[i] = g.C;
+    f32 = g.f32;
+    return SSAK_OK;
+  }
+  // grouped when the batch fills at least 5/8 of a round of 256 workgroups, else one by one (split-K: the last, partial launch
+  // of a backward and tiny test models)
+  int launch(int n, int tiles) {
+    int rc = SSAK_OK;
+    if (f32) {
+      for (int i = 0; i < n && rc == SSAK_OK; ++i) rc = ssak_gemm_f32(&d[i], A[i], B[i], C[i], nullptr, nullptr, nullptr, (void*)st);
+    } else if (tiles >= 160) {
+      rc = ssak_gemm_bf16_grouped(d, n, A, B, C, (void*)st);
+    } else {
+      for (int i = 0; i < n && rc == SSAK_OK; ++i) {
+        d[i].split_k = 0;
+        rc = ssak_gemm_bf16(&d[i], A[i], B[i], C[i], nullptr, nullptr, nullptr, slab, slab_bytes, (void*)st);
+      }
+    }
+    return rc;
+  }
+};
+inline int WgradLaunch::operator()(int n, int tiles) const { return q->launch(n, tiles); }
+// (unreachable from here: check_config bounds num_layers, and the head's range and every layer's fit in the FIFO together)
+static_assert(WgradQueue::ERR_RANGES == SSAK_ERR_STATE && WgradQueue::MAX_RANGES == SSAK_MAX_LAYERS + 1, "wgrad_schedule.h");
+
+// Partial-sum regions for the column reductions whose second stage is deferred (kernels.h: ReduceSink): while one of these
+// lives, the producers queue their second stages in its sink, and flush() runs them as one launch.  A region handed out stays
+// untouched until the next flush.
+struct ReduceRing {
+  ReduceSink sink;
+  float* const base;
+  const size_t floats;
+  const hipStream_t st;
+  size_t used = 0;
+  ReduceRing(float* base_, size_t floats_, hipStream_t st_) : base(base_), floats(floats_), st(st_) { g_reduce_sink = &sink; }
+  ~ReduceRing() { g_reduce_sink = nullptr; }  // what follows launches its second stages directly
+  ReduceRing(const ReduceRing&) = delete;
+  int flush() {
+    TRY(k_reduce_flush(sink, st));
+    used = 0;
+    return SSAK_OK;
+  }
+  int get(size_t nfloats, float** out) {
+    nfloats = (nfloats + 63) & ~(size_t)63;
+    // ring full: run what is queued and try once more.  The cadence of one flush per two KEPT layers keeps clear of this;
+    // a stable-LN model with many dropped layers reaches it (a dropped layer takes a region and does not advance the cadence)
+    if (used + nfloats > floats) TRY(flush());
+    if (used + nfloats > floats) {
+      ssak_set_error("w2v2_backward: reduction ring too small");
+      return SSAK_ERR_STATE;
+    }
+    *out = base + used;
+    used += nfloats;
+    return SSAK_OK;
+  }
+};
 
 struct ConvChain {
   int n;
@@ -693,16 +718,9 @@ int refresh_weight_fragments(ssak_w2v2* e, int M, const uint8_t* layer_keep, hip
   }
   if (e->wfrag_M != M) {
     for (int i = 0; i < 6; ++i) {
-      ssak_gemm_desc d;
-      memset(&d, 0, sizeof(d));
-      d.M = M, d.N = pr[i].N, d.K = pr[i].K;
-      d.b_kmajor = pr[i].b_km;
-      d.lda = pr[i].K, d.ldb = pr[i].ldb, d.ldc = pr[i].N;
-      d.nb1 = d.nb2 = 1;
-      d.alpha = 1.f;
-      d.split_k = 1;
-      d.pads_are_zero = 1;
-      e->wfrag_use[i] = ssak_gemm_uses_fragments(&d) != 0;
+      Gemm g(M, pr[i].N, pr[i].K);
+      g.a(nullptr, pr[i].K).b(nullptr, pr[i].ldb, pr[i].b_km != 0).c(nullptr, pr[i].N);
+      e->wfrag_use[i] = ssak_gemm_uses_fragments(&g.d) != 0;
     }
     e->wfrag_M = M;
   }
@@ -811,11 +829,7 @@ extern "C" void ssak_w2v2_destroy(ssak_w2v2* e) {
 }
 
 extern "C" long ssak_w2v2_num_params(const ssak_w2v2* e) { return e ? e->n_total : 0; }
-extern "C" long ssak_w2v2_num_trainable(const ssak_w2v2* e) {
-  if (!e) return 0;
-  if (e->cfg.arch == 1) return e->n_train;  // everything but the fixed position table
-  return e->cfg.freeze_feature_encoder ? e->n_train : e->n_total;
-}
+extern "C" long ssak_w2v2_num_trainable(const ssak_w2v2* e) { return e ? e->n_grad() : 0; }
 extern "C" int ssak_w2v2_param_count(const ssak_w2v2* e) { return e ? (int)e->params.size() : 0; }
 extern "C" int ssak_w2v2_param_info(const ssak_w2v2* e, int index, char* name, int name_cap, long* offset, long* numel,
                                     int* ndim, long* shape4) {
@@ -878,9 +892,7 @@ extern "C" int ssak_w2v2_grad_ranges(const ssak_w2v2_config* cfg, long* offsets,
   e.cfg = *cfg;
   build_param_table(&e);
   const ssak_w2v2_config& c = e.cfg;
-  const long H = c.hidden_size, I = c.intermediate_size, V = c.vocab_size;
-  const long n_grad = (c.arch == 1 || c.freeze_feature_encoder) ? e.n_train : e.n_total;
-  const long layer_span = (e.lp[0].w2 + H * I) - e.lp[0].wqkv;
+  const long H = c.hidden_size, V = c.vocab_size;
   int n = 0;
   auto put = [&](long off, long cnt) {
     if (cnt <= 0) return;
@@ -891,9 +903,9 @@ extern "C" int ssak_w2v2_grad_ranges(const ssak_w2v2_config* cfg, long* offsets,
     ++n;
   };
   put(e.p_lm_w, V * H);
-  for (int l = c.num_layers - 1; l >= 0; --l) put(e.lp[l].wqkv, layer_span);
+  for (int l = c.num_layers - 1; l >= 0; --l) put(e.lp[l].wqkv, e.layer_span());
   put(0, e.lp[0].wqkv);
-  put(e.p_lm_w + V * H, n_grad - (e.p_lm_w + V * H));
+  put(e.p_lm_w + V * H, e.n_grad() - (e.p_lm_w + V * H));
   return n;
 }
 
@@ -974,87 +986,122 @@ extern "C" int ssak_w2v2_num_frames(const ssak_w2v2* e, int T) {
   return L;
 }
 
-// logits != NULL: through final dropout + lm_head (Wav2Vec2ForCTC); hidden != NULL: the encoder's last hidden state
-// (Wav2Vec2Model()[0], what the SpeechBrain recipe's wav2vec2 module returns) and no head.
+// One forward or backward call on a handle: what its stages share, and the stages.  Made once the plan of the call's shape
+// exists and e->seed / e->lens are those of the forward in question.  AT is the activation storage type: bf16, or float in the
+// fp32-exact verification mode (ssak_w2v2_config.exact).
 template <typename AT>
-static int forward_impl(ssak_w2v2* e, const float* input_values, const int32_t* lens, int B, int T, const uint8_t* spec_mask,
-                        const uint8_t* layer_keep /*host*/, uint64_t seed, int training, float* logits, void* hidden /*AT [M, H]*/,
-                        int32_t* frame_lens, void* workspace, size_t workspace_bytes, void* stream) {
-  SSAK_REQUIRE(e && input_values && (logits || hidden) && workspace, "w2v2_forward: null pointer");
-  SSAK_REQUIRE(e->P && e->W, "w2v2_forward: bind + sync_weights first");
-  SSAK_REQUIRE(B > 0 && T > 0, "w2v2_forward: bad shape B=%d T=%d", B, T);
-  SSAK_REQUIRE(((uintptr_t)workspace & 255) == 0, "w2v2_forward: workspace must be 256-byte aligned");
-  SSAK_REQUIRE(!(training && e->cfg.adapter_attn_dim > 0),
-               "w2v2_forward: a model with language adapters (adapter_attn_dim > 0) runs inference only: training is not implemented");
-  constexpr bool EXACT = sizeof(AT) == 4;  // fp32-exact verification mode (ssak_w2v2_config.exact)
-  EngineCall engine_call(e);
-  Plan& p = e->plan;
-  e->have_fwd = false;
-  TRY(make_plan(e, B, T, training, p));
-  SSAK_REQUIRE(workspace_bytes >= p.total, "w2v2_forward: workspace too small (%zu < %zu)", workspace_bytes, p.total);
-  const ssak_w2v2_config& c = e->cfg;
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  auto BF = [&](size_t off) { return (AT*)(ws + off); };
-  auto FP = [&](size_t off) { return (float*)(ws + off); };
-  const int H = c.hidden_size, I = c.intermediate_size, V = c.vocab_size, nh = c.num_heads, hd = H / nh;
-  const bool whisper = c.arch == 1;
-  const int nc = whisper ? 1 : c.num_conv_layers, C = whisper ? 8 : c.conv_dim[nc - 1], K = whisper ? 8 : c.num_conv_pos_embeddings;
-  const int G = whisper ? 1 : c.num_conv_pos_embedding_groups, cg = H / G;
-  const int F = p.F, M = p.M, Fp = p.Fp;
-  const float* P = e->P;
-  const AT* W = EXACT ? (const AT*)e->P : (const AT*)e->W;  // exact mode: products read the fp32 master weights
-  e->seed = seed;
-  e->spec_mask = spec_mask;
-  e->lens = lens;
-  e->last_input = input_values;
-  const bool tr = training != 0;
-  auto DS = [&](float prob, uint32_t stream_id) {
+struct Call {
+  static constexpr bool EXACT = sizeof(AT) == 4;
+  ssak_w2v2* const e;
+  const ssak_w2v2_config& c;
+  const Plan& p;
+  char* const ws;
+  const hipStream_t st;
+  const bool tr;  // dropout sites draw masks: a training-mode forward, every backward
+  const uint64_t seed;
+  const bool whisper, stable;
+  const int H, I, V, nh, hd, nc, C, K, G, cg, B, F, M, Fp;
+  const float* const P;
+  float* const Gd;
+  const AT* const W;  // exact mode: products read the fp32 master weights
+  int32_t* const flens;  // frame lengths (attention / CTC masks), null without sample lengths
+  const float scale;
+  const DropSpec none;
+  void* const slab;        // split-K slabs of the weight-gradient products (training plan)
+  const size_t cs_floats;  // p.lnpart doubles as the column-sum scratch
+
+  Call(ssak_w2v2* e_, void* workspace, void* stream, bool training)
+      : e(e_), c(e_->cfg), p(e_->plan), ws((char*)workspace), st((hipStream_t)stream), tr(training), seed(e_->seed),
+        whisper(c.arch == 1), stable(whisper || c.do_stable_layer_norm != 0), H(c.hidden_size), I(c.intermediate_size),
+        V(c.vocab_size), nh(c.num_heads), hd(H / nh), nc(whisper ? 1 : c.num_conv_layers), C(whisper ? 8 : c.conv_dim[nc - 1]),
+        K(whisper ? 8 : c.num_conv_pos_embeddings), G(whisper ? 1 : c.num_conv_pos_embedding_groups), cg(H / G), B(p.B), F(p.F),
+        M(p.M), Fp(p.Fp), P(e_->P), Gd(e_->G), W(EXACT ? (const AT*)e_->P : (const AT*)e_->W),
+        flens(e_->lens ? (int32_t*)(ws + p.flens) : nullptr), scale(1.f / sqrtf((float)hd)), slab(ws + p.slab),
+        cs_floats((size_t)LN_BWD_BLOCKS * 3 * std::max(H, C)) {}
+
+  AT* BF(size_t off) const { return (AT*)(ws + off); }
+  float* FP(size_t off) const { return (float*)(ws + off); }
+  DropSpec DS(float prob, uint32_t stream_id) const {
     DropSpec d;
     d.seed = seed;
     d.stream = stream_id;
     d.p = tr ? prob : 0.f;
     return d;
-  };
-  const DropSpec none;
-  // the optimizer may still be updating params / shadow on its own stream (ssak_w2v2_set_param_event)
-  bool waited = false;
-  auto wait_params = [&]() -> int {
-    if (waited || !e->params_ready) return SSAK_OK;
-    waited = true;
-    if (e->stall_begin) SSAK_HIP(hipEventRecord(e->stall_begin, st));
-    SSAK_HIP(hipStreamWaitEvent(st, e->params_ready, 0));
-    if (e->stall_end) SSAK_HIP(hipEventRecord(e->stall_end, st));
-    return SSAK_OK;
-  };
-  // conv1 of the Whisper front end and an unfrozen feature encoder are trainable: wait before anything runs
-  if (whisper || !c.freeze_feature_encoder) TRY(wait_params());
+  }
+  // LayerNorm that produces the next layer's input in stable mode (next layer's LN1, or the encoder's final LN)
+  long next_ln_w(int l) const { return (l + 1 < c.num_layers) ? e->lp[l + 1].ln1w : e->p_eln_w; }
+  long next_ln_b(int l) const { return (l + 1 < c.num_layers) ? e->lp[l + 1].ln1b : e->p_eln_b; }
 
-  int32_t* flens = nullptr;
-  const bool stable = whisper || c.do_stable_layer_norm != 0;
-  if (whisper) {
-   {
-    // ---- a14 front end: mel [B, NM, Tin] -> channels-last padded -> conv1+GELU -> conv2(s2)+GELU -> + positions
-    const int NM = c.num_mel_bins, Tin = p.Tin, RS1 = p.RS1;
-    SSAK_REQUIRE(!lens, "whisper: fixed-length windows, no attention mask (modeling_whisper.py:605-607)");
-    SSAK_HIP(hipMemsetAsync(ws + p.melcl, 0, ((size_t)B * RS1 + 8) * NM * sizeof(AT), st));
-    SSAK_HIP(hipMemsetAsync(ws + p.h1pad, 0, ((size_t)B * RS1 + 8) * H * sizeof(AT), st));
-    TRY(k_mel_to_cl_t<AT>(input_values, BF(p.melcl), B, NM, Tin, RS1, 1, st));
-    TRY(GemmX<EXACT>(Tin, H, 3 * NM).a(BF(p.melcl), NM).b(e->conv_w[1], 3 * NM).c(BF(p.h1pad) + H, H)
-            .batch(B, 1, (long)RS1 * NM, 0, 0, 0, (long)RS1 * H, 0).with_bias(P + e->p_c1b)
-            .epi(SSAK_EPI_GELU, nullptr, BF(p.pre1) + H).run(st));
-    TRY(GemmX<EXACT>(F, H, 3 * H).a(BF(p.h1pad), 2 * H).b(e->conv_w[2], 3 * H).c(BF(p.we), H)
-            .batch(B, 1, (long)RS1 * H, 0, 0, 0, (long)F * H, 0).with_bias(P + e->p_c2b)
-            .epi(SSAK_EPI_GELU, nullptr, BF(p.wpre2)).run(st));
-    TRY(k_add_rowvec_t<AT>(BF(p.we), W + e->p_pos, BF(p.h1), B, F, H, st));
-    // residual stream r = dropout(conv + pos); x0 = self_attn_layer_norm of layer 0
-    TRY(k_layernorm_fwd_t<AT>(BF(p.h1), nullptr, P + e->lp[0].ln1w, P + e->lp[0].ln1b, BF(p.h1), BF(p.x[0]), FP(p.stE),
-                        FP(p.stE) + M, M, H, c.layer_norm_eps, none, none, st, DS(c.hidden_dropout, DS_ENCIN)));
-   }
-  } else {
+  // ---- forward, in this order
+  bool waited = false;
+  int wait_params();
+  int fwd_whisper_frontend(const float* input_values);
+  int fwd_features(const float* input_values, const int32_t* lens, int32_t* frame_lens);
+  int fwd_posconv_encoder_input();
+  int fwd_layer(int l, bool skip);
+  int fwd_head(float* logits, void* hidden);
+
+  // ---- backward, in this order.  gA (+gB) = gradient w.r.t. x[l+1], the layer output (post-LN) or the normalised input of
+  // the next layer (stable-LN); Gres = gradient of the residual stream (stable-LN only).
+  AT* gA = nullptr;
+  AT* gB = nullptr;
+  const AT* Gres = nullptr;
+  int kept = 0;  // layers that ran so far: selects the buffer set their weight-gradient operands live in
+  AT* free_buf(const AT* u1, const AT* u2, const AT* u3) const {
+    AT* cand[3] = {BF(p.dC), BF(p.dA), BF(p.scratchH)};
+    for (AT* cnd : cand)
+      if (cnd != u1 && cnd != u2 && cnd != u3) return cnd;
+    return (AT*)nullptr;
+  }
+  void announce(long off, long cnt) const { WgradAnnounce{e}(off, cnt); }
+  int bwd_zero_grads();
+  int bwd_head(const float* dlogits, const void* dhidden, WgradQueue& wq);
+  int bwd_layer(int l, WgradQueue& wq, ReduceRing& red);
+  int bwd_dropped_layer(int l, WgradQueue& wq, ReduceRing& red);
+  int bwd_encoder_input(AT** dh1);
+  int bwd_whisper_frontend(AT* dh1);
+  int bwd_posconv_projection(AT* dh1);
+  int bwd_feature_encoder();
+};
+
+// the optimizer may still be updating params / shadow on its own stream (ssak_w2v2_set_param_event)
+template <typename AT>
+int Call<AT>::wait_params() {
+  if (waited || !e->params_ready) return SSAK_OK;
+  waited = true;
+  if (e->stall_begin) SSAK_HIP(hipEventRecord(e->stall_begin, st));
+  SSAK_HIP(hipStreamWaitEvent(st, e->params_ready, 0));
+  if (e->stall_end) SSAK_HIP(hipEventRecord(e->stall_end, st));
+  return SSAK_OK;
+}
+
+template <typename AT>
+int Call<AT>::fwd_whisper_frontend(const float* input_values) {
+  // ---- a14 front end: mel [B, NM, Tin] -> channels-last padded -> conv1+GELU -> conv2(s2)+GELU -> + positions
+  const int NM = c.num_mel_bins, Tin = p.Tin, RS1 = p.RS1;
+  SSAK_REQUIRE(!e->lens, "whisper: fixed-length windows, no attention mask (modeling_whisper.py:605-607)");
+  SSAK_HIP(hipMemsetAsync(ws + p.melcl, 0, ((size_t)B * RS1 + 8) * NM * sizeof(AT), st));
+  SSAK_HIP(hipMemsetAsync(ws + p.h1pad, 0, ((size_t)B * RS1 + 8) * H * sizeof(AT), st));
+  TRY(k_mel_to_cl_t<AT>(input_values, BF(p.melcl), B, NM, Tin, RS1, 1, st));
+  TRY(GemmX<EXACT>(Tin, H, 3 * NM).a(BF(p.melcl), NM).b(e->conv_w[1], 3 * NM).c(BF(p.h1pad) + H, H)
+          .batch(B, 1, (long)RS1 * NM, 0, 0, 0, (long)RS1 * H, 0).with_bias(P + e->p_c1b)
+          .epi(SSAK_EPI_GELU, nullptr, BF(p.pre1) + H).run(st));
+  TRY(GemmX<EXACT>(F, H, 3 * H).a(BF(p.h1pad), 2 * H).b(e->conv_w[2], 3 * H).c(BF(p.we), H)
+          .batch(B, 1, (long)RS1 * H, 0, 0, 0, (long)F * H, 0).with_bias(P + e->p_c2b)
+          .epi(SSAK_EPI_GELU, nullptr, BF(p.wpre2)).run(st));
+  TRY(k_add_rowvec_t<AT>(BF(p.we), W + e->p_pos, BF(p.h1), B, F, H, st));
+  // residual stream r = dropout(conv + pos); x0 = self_attn_layer_norm of layer 0
+  TRY(k_layernorm_fwd_t<AT>(BF(p.h1), nullptr, P + e->lp[0].ln1w, P + e->lp[0].ln1b, BF(p.h1), BF(p.x[0]), FP(p.stE),
+                      FP(p.stE) + M, M, H, c.layer_norm_eps, none, none, st, DS(c.hidden_dropout, DS_ENCIN)));
+  return SSAK_OK;
+}
+
+// wav2vec2 front end up to the SpecAugment scatter: feature encoder, feature projection, masked_spec_embed
+template <typename AT>
+int Call<AT>::fwd_features(const float* input_values, const int32_t* lens, int32_t* frame_lens) {
+  const int T = p.T;
   // frame lengths (attention / CTC masks) from sample lengths: integer floor-div chain (modeling_wav2vec2.py:997-1016)
   if (lens) {
-    flens = (int32_t*)(ws + p.flens);
     ConvChain cc;
     cc.n = nc;
     for (int i = 0; i < nc; ++i) {
@@ -1112,7 +1159,12 @@ static int forward_impl(ssak_w2v2* e, const float* input_values, const int32_t* 
       TRY(k_layernorm_fwd_t<AT>(BF(p.h0), nullptr, nullptr, nullptr, BF(p.h0), nullptr, nullptr, nullptr, M, H, 0.f,
                           DS(c.feat_proj_dropout, DS_FEATPROJ), none, st));
   // ---- a5: SpecAugment scatter + zeroing of padded frames
-  TRY(k_specaug_fwd_t<AT>(BF(p.h0), spec_mask, flens, P + e->p_mse, B, F, H, st));
+  TRY(k_specaug_fwd_t<AT>(BF(p.h0), e->spec_mask, flens, P + e->p_mse, B, F, H, st));
+  return SSAK_OK;
+}
+
+template <typename AT>
+int Call<AT>::fwd_posconv_encoder_input() {
   // ---- a6: positional conv (grouped, weight-normed) + GELU, residual, LayerNorm, dropout
   TRY(k_posconv_pack_t<AT>(BF(p.h0), BF(p.pgx), B, F, H, G, K, st));
   bool pc_direct = false;
@@ -1140,92 +1192,83 @@ static int forward_impl(ssak_w2v2* e, const float* input_values, const int32_t* 
     TRY(k_layernorm_fwd_t<AT>(BF(p.pc), BF(p.h0), P + e->lp[0].ln1w, P + e->lp[0].ln1b, BF(p.h1), BF(p.x[0]), FP(p.stE),
                         FP(p.stE) + M, M, H, c.layer_norm_eps, none, none, st, DS(c.hidden_dropout, DS_ENCIN)));
   }
-  }
-  // ---- a7: encoder layers with LayerDrop: post-LN (base, :591-608) or pre-LN "stable layer norm" (XLSR, :631-654)
-  e->keep.assign(c.num_layers, 1);
-  e->wfrag_valid = false;
-  if constexpr (!EXACT) {
-    // fragment-ordered weights of the layers that will run, for the products that take the B-direct GEMM form (the optimizer's
-    // event has been waited for above: the shadow is final)
-    if (tr && e->fragment_weights) TRY(refresh_weight_fragments(e, M, layer_keep, st));
-  }
-  e->wtr_valid = false;
-  if constexpr (!EXACT) {
-    // transposed weights for the backward's input-gradient products (the four-wave GEMM wants both operands K-contiguous)
-    if (tr && e->transposed_weights && c.hidden_size % 256 == 0 && c.intermediate_size % 256 == 0) TRY(refresh_weight_transposes(e, layer_keep, st));
-  }
-  e->hres.assign(c.num_layers + 1, p.h1);
-  e->xin[0] = p.x[0];
-  const float scale = 1.f / sqrtf((float)hd);
-  for (int l = 0; l < c.num_layers; ++l) {
-    const LayerP& L = e->lp[l];
-    const LayerBuf& lb = p.lb[l];
-    float* stl = FP(lb.st);
-    // LayerNorm that produces the next layer's input in stable mode (next layer's LN1, or the encoder's final LN)
-    const float* nxt_w = P + ((l + 1 < c.num_layers) ? e->lp[l + 1].ln1w : e->p_eln_w);
-    const float* nxt_b = P + ((l + 1 < c.num_layers) ? e->lp[l + 1].ln1b : e->p_eln_b);
-    if (tr && layer_keep && !layer_keep[l]) {
-      e->keep[l] = 0;
-      if (!stable) {
-        // skipped layer: output = input (modeling_wav2vec2.py:701-712) -- the next layer reads this layer's input where it lies
-        // (it used to be a 24.5 MB device copy per dropped layer)
-        e->xin[l + 1] = e->xin[l];
-      } else {
-        // the residual stream passes through; the next LayerNorm still has to be applied to it
-        TRY(k_layernorm_fwd_t<AT>(BF(e->hres[l]), nullptr, nxt_w, nxt_b, nullptr, BF(p.x[l + 1]), stl + 2 * M, stl + 3 * M, M, H,
-                            c.layer_norm_eps, none, none, st));
-        e->hres[l + 1] = e->hres[l];
-        e->xin[l + 1] = p.x[l + 1];
-      }
-      continue;
-    }
-    const AT* x = BF(e->xin[l]);
-    e->xin[l + 1] = p.x[l + 1];
-    AT* qkv = BF(lb.qkv);
-    TRY(GemmX<EXACT>(M, 3 * H, H).a(x, H).b(W + L.wqkv, H).bfrag(e->frag(l, 0)).c(qkv, 3 * H).with_bias(P + L.bqkv).run(st));
-    if (p.fused_attn) {
-      // scores never leave the MFMA accumulators (attention.hip); only ctx and the per-row log-sum-exp are written
-      if constexpr (!EXACT)
-        TRY(k_attention_fwd(qkv, BF(lb.ctx), FP(lb.lse), flens, B, F, nh, H, DS(c.attention_dropout, ds_attn(l)), st));
-    } else {
-      TRY(GemmX<EXACT>(F, F, hd).a(qkv, 3 * H).b(qkv + H, 3 * H).c(BF(p.S), Fp).alpha(scale)
-              .batch(B, nh, (long)F * 3 * H, hd, (long)F * 3 * H, hd, (long)nh * F * Fp, (long)F * Fp).run(st));
-      TRY(k_softmax_fwd_t<AT>(BF(p.S), BF(lb.P), lb.Pd != lb.P ? BF(lb.Pd) : nullptr, flens, B * nh * F, F, Fp, nh * F,
-                        DS(c.attention_dropout, ds_attn(l)), st));
-      TRY(GemmX<EXACT>(F, hd, F).a(BF(lb.Pd), Fp).b(qkv + 2 * H, 3 * H, true).c(BF(lb.ctx), H)
-              .batch(B, nh, (long)nh * F * Fp, (long)F * Fp, (long)F * 3 * H, hd, (long)F * H, hd).run(st));
-    }
-    TRY(GemmX<EXACT>(M, H, H).a(BF(lb.ctx), H).b(W + L.wo, H).bfrag(e->frag(l, 1)).c(BF(p.tmpH), H).with_bias(P + L.bo).run(st));
+  return SSAK_OK;
+}
+
+// ---- a7: one encoder layer, or what LayerDrop leaves of it: post-LN (base, :591-608) or pre-LN "stable layer norm" (XLSR, :631-654)
+template <typename AT>
+int Call<AT>::fwd_layer(int l, bool skip) {
+  const LayerP& L = e->lp[l];
+  const LayerBuf& lb = p.lb[l];
+  float* stl = FP(lb.st);
+  const float* nxt_w = P + next_ln_w(l);
+  const float* nxt_b = P + next_ln_b(l);
+  if (skip) {
+    e->keep[l] = 0;
     if (!stable) {
-      TRY(k_layernorm_fwd_t<AT>(BF(p.tmpH), x, P + L.ln1w, P + L.ln1b, BF(lb.r1), BF(lb.x1), stl, stl + M, M, H,
-                          c.layer_norm_eps, DS(c.hidden_dropout, ds_hid1(l)), none, st));
+      // skipped layer: output = input (modeling_wav2vec2.py:701-712) -- the next layer reads this layer's input where it lies
+      // (it used to be a 24.5 MB device copy per dropped layer)
+      e->xin[l + 1] = e->xin[l];
     } else {
-      // r1 = r + drop(attn);  x1 = final_layer_norm(r1)
-      TRY(k_layernorm_fwd_t<AT>(BF(p.tmpH), BF(e->hres[l]), P + L.ln2w, P + L.ln2b, BF(lb.r1), BF(lb.x1), stl, stl + M, M, H,
-                          c.layer_norm_eps, DS(c.hidden_dropout, ds_hid1(l)), none, st));
+      // the residual stream passes through; the next LayerNorm still has to be applied to it
+      TRY(k_layernorm_fwd_t<AT>(BF(e->hres[l]), nullptr, nxt_w, nxt_b, nullptr, BF(p.x[l + 1]), stl + 2 * M, stl + 3 * M, M, H,
+                          c.layer_norm_eps, none, none, st));
+      e->hres[l + 1] = e->hres[l];
+      e->xin[l + 1] = p.x[l + 1];
     }
-    TRY(GemmX<EXACT>(M, I, H).a(BF(lb.x1), H).b(W + L.w1, H).c(BF(lb.f1), I).with_bias(P + L.b1)
-            .epi(tr ? SSAK_EPI_GELU_SAVE_GRAD : SSAK_EPI_GELU, nullptr, tr ? BF(lb.f1pre) : nullptr)  // f1pre := 8-bit codes of gelu'(pre) * mask (float values incl. 1 / (1 - p) in the exact mode)
-            .drop(tr ? c.activation_dropout : 0.f, ds_act(l), seed).run(st));
-    TRY(GemmX<EXACT>(M, H, I).a(BF(lb.f1), I).b(W + L.w2, I).bfrag(e->frag(l, 2)).c(BF(p.tmpH), H).with_bias(P + L.b2).run(st));
-    if (!stable) {
-      TRY(k_layernorm_fwd_t<AT>(BF(p.tmpH), BF(lb.x1), P + L.ln2w, P + L.ln2b, BF(lb.r2), BF(p.x[l + 1]), stl + 2 * M, stl + 3 * M,
-                          M, H, c.layer_norm_eps, DS(c.hidden_dropout, ds_hid2(l)), none, st));
-    } else {
-      // r2 = r1 + drop(ffn);  x[l+1] = (next layer's LN1 | encoder LN)(r2)
-      if (c.adapter_attn_dim > 0)
-        // ... with the language adapter between them: r2' = r2 + adapter(r2), x[l+1] = LN(r2') (attn_adapter.hip; inference
-        // only, so no dropout site; the adapter's LayerNorm is a plain nn.LayerNorm: eps 1e-5, not layer_norm_eps)
-        TRY(k_attn_adapter_fwd_t<AT>(BF(p.tmpH), BF(lb.r1), P + L.ad_nw, P + L.ad_nb, W + L.ad_w1, P + L.ad_b1, W + L.ad_w2, P + L.ad_b2,
-                                     nxt_w, nxt_b, BF(lb.r2), BF(p.x[l + 1]), stl + 2 * M, stl + 3 * M, M, H, c.adapter_attn_dim, 1e-5f,
-                                     c.layer_norm_eps, st));
-      else
-        TRY(k_layernorm_fwd_t<AT>(BF(p.tmpH), BF(lb.r1), nxt_w, nxt_b, BF(lb.r2), BF(p.x[l + 1]), stl + 2 * M, stl + 3 * M, M, H,
-                            c.layer_norm_eps, DS(c.hidden_dropout, ds_hid2(l)), none, st));
-      e->hres[l + 1] = lb.r2;
-    }
+    return SSAK_OK;
   }
-  // ---- a8: final dropout + lm_head -> fp32 logits
+  const AT* x = BF(e->xin[l]);
+  e->xin[l + 1] = p.x[l + 1];
+  AT* qkv = BF(lb.qkv);
+  TRY(GemmX<EXACT>(M, 3 * H, H).a(x, H).b(W + L.wqkv, H).bfrag(e->frag(l, 0)).c(qkv, 3 * H).with_bias(P + L.bqkv).run(st));
+  if (p.fused_attn) {
+    // scores never leave the MFMA accumulators (attention.hip); only ctx and the per-row log-sum-exp are written
+    if constexpr (!EXACT)
+      TRY(k_attention_fwd(qkv, BF(lb.ctx), FP(lb.lse), flens, B, F, nh, H, DS(c.attention_dropout, ds_attn(l)), st));
+  } else {
+    TRY(GemmX<EXACT>(F, F, hd).a(qkv, 3 * H).b(qkv + H, 3 * H).c(BF(p.S), Fp).alpha(scale)
+            .batch(B, nh, (long)F * 3 * H, hd, (long)F * 3 * H, hd, (long)nh * F * Fp, (long)F * Fp).run(st));
+    TRY(k_softmax_fwd_t<AT>(BF(p.S), BF(lb.P), lb.Pd != lb.P ? BF(lb.Pd) : nullptr, flens, B * nh * F, F, Fp, nh * F,
+                      DS(c.attention_dropout, ds_attn(l)), st));
+    TRY(GemmX<EXACT>(F, hd, F).a(BF(lb.Pd), Fp).b(qkv + 2 * H, 3 * H, true).c(BF(lb.ctx), H)
+            .batch(B, nh, (long)nh * F * Fp, (long)F * Fp, (long)F * 3 * H, hd, (long)F * H, hd).run(st));
+  }
+  TRY(GemmX<EXACT>(M, H, H).a(BF(lb.ctx), H).b(W + L.wo, H).bfrag(e->frag(l, 1)).c(BF(p.tmpH), H).with_bias(P + L.bo).run(st));
+  if (!stable) {
+    TRY(k_layernorm_fwd_t<AT>(BF(p.tmpH), x, P + L.ln1w, P + L.ln1b, BF(lb.r1), BF(lb.x1), stl, stl + M, M, H,
+                        c.layer_norm_eps, DS(c.hidden_dropout, ds_hid1(l)), none, st));
+  } else {
+    // r1 = r + drop(attn);  x1 = final_layer_norm(r1)
+    TRY(k_layernorm_fwd_t<AT>(BF(p.tmpH), BF(e->hres[l]), P + L.ln2w, P + L.ln2b, BF(lb.r1), BF(lb.x1), stl, stl + M, M, H,
+                        c.layer_norm_eps, DS(c.hidden_dropout, ds_hid1(l)), none, st));
+  }
+  TRY(GemmX<EXACT>(M, I, H).a(BF(lb.x1), H).b(W + L.w1, H).c(BF(lb.f1), I).with_bias(P + L.b1)
+          .epi(tr ? SSAK_EPI_GELU_SAVE_GRAD : SSAK_EPI_GELU, nullptr, tr ? BF(lb.f1pre) : nullptr)  // f1pre := 8-bit codes of gelu'(pre) * mask (float values incl. 1 / (1 - p) in the exact mode)
+          .drop(tr ? c.activation_dropout : 0.f, ds_act(l), seed).run(st));
+  TRY(GemmX<EXACT>(M, H, I).a(BF(lb.f1), I).b(W + L.w2, I).bfrag(e->frag(l, 2)).c(BF(p.tmpH), H).with_bias(P + L.b2).run(st));
+  if (!stable) {
+    TRY(k_layernorm_fwd_t<AT>(BF(p.tmpH), BF(lb.x1), P + L.ln2w, P + L.ln2b, BF(lb.r2), BF(p.x[l + 1]), stl + 2 * M, stl + 3 * M,
+                        M, H, c.layer_norm_eps, DS(c.hidden_dropout, ds_hid2(l)), none, st));
+  } else {
+    // r2 = r1 + drop(ffn);  x[l+1] = (next layer's LN1 | encoder LN)(r2)
+    if (c.adapter_attn_dim > 0)
+      // ... with the language adapter between them: r2' = r2 + adapter(r2), x[l+1] = LN(r2') (attn_adapter.hip; inference
+      // only, so no dropout site; the adapter's LayerNorm is a plain nn.LayerNorm: eps 1e-5, not layer_norm_eps)
+      TRY(k_attn_adapter_fwd_t<AT>(BF(p.tmpH), BF(lb.r1), P + L.ad_nw, P + L.ad_nb, W + L.ad_w1, P + L.ad_b1, W + L.ad_w2, P + L.ad_b2,
+                                   nxt_w, nxt_b, BF(lb.r2), BF(p.x[l + 1]), stl + 2 * M, stl + 3 * M, M, H, c.adapter_attn_dim, 1e-5f,
+                                   c.layer_norm_eps, st));
+    else
+      TRY(k_layernorm_fwd_t<AT>(BF(p.tmpH), BF(lb.r1), nxt_w, nxt_b, BF(lb.r2), BF(p.x[l + 1]), stl + 2 * M, stl + 3 * M, M, H,
+                          c.layer_norm_eps, DS(c.hidden_dropout, ds_hid2(l)), none, st));
+    e->hres[l + 1] = lb.r2;
+  }
+  return SSAK_OK;
+}
+
+// ---- a8: final dropout + lm_head -> fp32 logits, or the last hidden state as it is
+template <typename AT>
+int Call<AT>::fwd_head(float* logits, void* hidden) {
   const AT* xl = BF(e->xin[c.num_layers]);
   if (hidden) {
     SSAK_HIP(hipMemcpyAsync(hidden, xl, (size_t)M * H * sizeof(AT), hipMemcpyDeviceToDevice, st));  // (float in the fp32-exact mode)
@@ -1242,6 +1285,54 @@ static int forward_impl(ssak_w2v2* e, const float* input_values, const int32_t* 
   TRY(GemmX<EXACT>(M, V, H).a(xl, H).b(W + e->p_lm_w, H).c(logits, V, true).with_bias(P + e->p_lm_b).run(st));
   e->have_fwd = tr;
   return SSAK_OK;
+}
+
+// logits != NULL: through final dropout + lm_head (Wav2Vec2ForCTC); hidden != NULL: the encoder's last hidden state
+// (Wav2Vec2Model()[0], what the SpeechBrain recipe's wav2vec2 module returns) and no head.
+template <typename AT>
+static int forward_impl(ssak_w2v2* e, const float* input_values, const int32_t* lens, int B, int T, const uint8_t* spec_mask,
+                        const uint8_t* layer_keep /*host*/, uint64_t seed, int training, float* logits, void* hidden /*AT [M, H]*/,
+                        int32_t* frame_lens, void* workspace, size_t workspace_bytes, void* stream) {
+  SSAK_REQUIRE(e && input_values && (logits || hidden) && workspace, "w2v2_forward: null pointer");
+  SSAK_REQUIRE(e->P && e->W, "w2v2_forward: bind + sync_weights first");
+  SSAK_REQUIRE(B > 0 && T > 0, "w2v2_forward: bad shape B=%d T=%d", B, T);
+  SSAK_REQUIRE(((uintptr_t)workspace & 255) == 0, "w2v2_forward: workspace must be 256-byte aligned");
+  SSAK_REQUIRE(!(training && e->cfg.adapter_attn_dim > 0),
+               "w2v2_forward: a model with language adapters (adapter_attn_dim > 0) runs inference only: training is not implemented");
+  EngineCall engine_call(e);
+  e->have_fwd = false;
+  TRY(make_plan(e, B, T, training, e->plan));
+  SSAK_REQUIRE(workspace_bytes >= e->plan.total, "w2v2_forward: workspace too small (%zu < %zu)", workspace_bytes, e->plan.total);
+  e->seed = seed;
+  e->spec_mask = spec_mask;
+  e->lens = lens;
+  e->last_input = input_values;
+  Call<AT> k(e, workspace, stream, training != 0);
+  const ssak_w2v2_config& c = e->cfg;
+  // conv1 of the Whisper front end and an unfrozen feature encoder are trainable: wait before anything runs
+  if (k.whisper || !c.freeze_feature_encoder) TRY(k.wait_params());
+  if (k.whisper) {
+    TRY(k.fwd_whisper_frontend(input_values));
+  } else {
+    TRY(k.fwd_features(input_values, lens, frame_lens));
+    TRY(k.fwd_posconv_encoder_input());
+  }
+  e->keep.assign(c.num_layers, 1);
+  e->wfrag_valid = false;
+  if constexpr (!Call<AT>::EXACT) {
+    // fragment-ordered weights of the layers that will run, for the products that take the B-direct GEMM form (the optimizer's
+    // event has been waited for above: the shadow is final)
+    if (k.tr && e->fragment_weights) TRY(refresh_weight_fragments(e, k.M, layer_keep, k.st));
+  }
+  e->wtr_valid = false;
+  if constexpr (!Call<AT>::EXACT) {
+    // transposed weights for the backward's input-gradient products (the four-wave GEMM wants both operands K-contiguous)
+    if (k.tr && e->transposed_weights && c.hidden_size % 256 == 0 && c.intermediate_size % 256 == 0) TRY(refresh_weight_transposes(e, layer_keep, k.st));
+  }
+  e->hres.assign(c.num_layers + 1, k.p.h1);
+  e->xin[0] = k.p.x[0];
+  for (int l = 0; l < c.num_layers; ++l) TRY(k.fwd_layer(l, k.tr && layer_keep && !layer_keep[l]));
+  return k.fwd_head(logits, hidden);
 }
 
 extern "C" int ssak_w2v2_forward(ssak_w2v2* e, const float* input_values, const int32_t* lens, int B, int T,
@@ -1268,68 +1359,29 @@ extern "C" int ssak_w2v2_forward_hidden(ssak_w2v2* e, const float* input_values,
                       workspace, workspace_bytes, stream);
 }
 
-// dlogits (after ssak_w2v2_forward) or dhidden (after ssak_w2v2_forward_hidden): exactly one is non-null
 template <typename AT>
-static int backward_impl(ssak_w2v2* e, const float* dlogits, const void* dhidden /*AT [M, H]*/, void* workspace, size_t workspace_bytes,
-                         void* stream) {
-  SSAK_REQUIRE(e && (dlogits || dhidden) && workspace, "w2v2_backward: null pointer");
-  SSAK_REQUIRE(e->cfg.adapter_attn_dim == 0,
-               "w2v2_backward: a model with language adapters (adapter_attn_dim > 0) runs inference only: training is not implemented");
-  if (!e->have_fwd || e->fwd_hidden != (dhidden != nullptr)) {
-    ssak_set_error("w2v2_backward: no matching training-mode forward to differentiate");
-    return SSAK_ERR_STATE;
+int Call<AT>::bwd_zero_grads() {
+  // Zero what is ACCUMULATED into (bias / LayerNorm / embedding gradients: everything outside the layers' weight matrices)
+  // and the matrices of dropped layers; the four matrices of a kept layer are written whole by its weight-gradient products
+  // (94 % of the buffer: 40 us of memset per step).  Falls back to the whole buffer if the layers are not laid out back to back.
+  const long span = e->layer_span(), n_grad = e->n_grad();
+  bool packed = true;
+  for (int l = 1; l < c.num_layers; ++l) packed &= e->lp[l].wqkv == e->lp[l - 1].wqkv + span;
+  const long w0 = e->lp[0].wqkv, w1 = e->lp[c.num_layers - 1].wqkv + span;
+  if (!packed || w1 > n_grad) {
+    SSAK_HIP(hipMemsetAsync(Gd, 0, (size_t)n_grad * sizeof(float), st));
+  } else {
+    if (w0 > 0) SSAK_HIP(hipMemsetAsync(Gd, 0, (size_t)w0 * sizeof(float), st));
+    for (int l = 0; l < c.num_layers; ++l)
+      if (!e->keep[l]) SSAK_HIP(hipMemsetAsync(Gd + e->lp[l].wqkv, 0, (size_t)span * sizeof(float), st));
+    if (n_grad > w1) SSAK_HIP(hipMemsetAsync(Gd + w1, 0, (size_t)(n_grad - w1) * sizeof(float), st));
   }
-  constexpr bool EXACT = sizeof(AT) == 4;
-  EngineCall engine_call(e);
-  SSAK_REQUIRE(e->G, "w2v2_backward: no gradient buffer bound");
-  Plan& p = e->plan;
-  SSAK_REQUIRE(workspace_bytes >= p.total, "w2v2_backward: workspace too small");
-  const ssak_w2v2_config& c = e->cfg;
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  auto BF = [&](size_t off) { return (AT*)(ws + off); };
-  auto FP = [&](size_t off) { return (float*)(ws + off); };
-  const int H = c.hidden_size, I = c.intermediate_size, V = c.vocab_size, nh = c.num_heads, hd = H / nh;
-  const bool whisper = c.arch == 1;
-  const int nc = whisper ? 1 : c.num_conv_layers, C = whisper ? 8 : c.conv_dim[nc - 1], K = whisper ? 8 : c.num_conv_pos_embeddings;
-  const int G = whisper ? 1 : c.num_conv_pos_embedding_groups, cg = H / G;
-  const int B = p.B, F = p.F, M = p.M, Fp = p.Fp;
-  const float* P = e->P;
-  float* Gd = e->G;
-  const AT* W = EXACT ? (const AT*)e->P : (const AT*)e->W;  // exact mode: products read the fp32 master weights
-  const uint64_t seed = e->seed;
-  const int32_t* flens = e->lens ? (const int32_t*)(ws + p.flens) : nullptr;
-  auto DS = [&](float prob, uint32_t stream_id) {
-    DropSpec d;
-    d.seed = seed;
-    d.stream = stream_id;
-    d.p = prob;
-    return d;
-  };
-  const DropSpec none;
-  void* slab = ws + p.slab;
-  const size_t cs_floats = (size_t)LN_BWD_BLOCKS * 3 * std::max(H, C);  // p.lnpart doubles as the column-sum scratch
-  const float scale = 1.f / sqrtf((float)hd);
+  return SSAK_OK;
+}
 
-  const long n_grad = (e->cfg.arch == 1 || e->cfg.freeze_feature_encoder) ? e->n_train : e->n_total;
-  {
-    // Zero what is ACCUMULATED into (bias / LayerNorm / embedding gradients: everything outside the layers' weight matrices)
-    // and the matrices of dropped layers; the four matrices of a kept layer are written whole by its weight-gradient products
-    // (94 % of the buffer: 40 us of memset per step).  Falls back to the whole buffer if the layers are not laid out back to back.
-    const long span = (e->lp[0].w2 + (long)c.hidden_size * c.intermediate_size) - e->lp[0].wqkv;
-    bool packed = true;
-    for (int l = 1; l < c.num_layers; ++l) packed &= e->lp[l].wqkv == e->lp[l - 1].wqkv + span;
-    const long w0 = e->lp[0].wqkv, w1 = e->lp[c.num_layers - 1].wqkv + span;
-    if (!packed || w1 > n_grad) {
-      SSAK_HIP(hipMemsetAsync(Gd, 0, (size_t)n_grad * sizeof(float), st));
-    } else {
-      if (w0 > 0) SSAK_HIP(hipMemsetAsync(Gd, 0, (size_t)w0 * sizeof(float), st));
-      for (int l = 0; l < c.num_layers; ++l)
-        if (!e->keep[l]) SSAK_HIP(hipMemsetAsync(Gd + e->lp[l].wqkv, 0, (size_t)span * sizeof(float), st));
-      if (n_grad > w1) SSAK_HIP(hipMemsetAsync(Gd + w1, 0, (size_t)(n_grad - w1) * sizeof(float), st));
-    }
-  }
-  // ---- lm_head (its gradient stays zero when the backward starts from the hidden state)
+// ---- lm_head (its gradient stays zero when the backward starts from the hidden state)
+template <typename AT>
+int Call<AT>::bwd_head(const float* dlogits, const void* dhidden, WgradQueue& wq) {
   AT* dlog = BF(p.dlog);
   if (dlogits) {
     if constexpr (EXACT)
@@ -1337,16 +1389,12 @@ static int backward_impl(ssak_w2v2* e, const float* dlogits, const void* dhidden
     else
       TRY(k_cast_f32_bf16(dlogits, dlog, (long)M * V, st));
     // (the lm_head weight gradient -- V x H, K = M: three tiles -- rides in the first grouped weight-gradient launch below instead of
-    // running alone as a split-K product with its slab reduction: queued once the queue exists)
+    // running alone as a split-K product with its slab reduction: queued at the end of this stage)
     TRY(k_colsum_t<AT>(dlog, V, M, V, Gd + e->p_lm_b, st, FP(p.lnpart), cs_floats));
   }
-  auto announce = [&](long off, long cnt) {
-    if (e->on_ready && cnt > 0) e->on_ready(off, cnt, e->on_ready_user);
-  };
-  const long layer_span = (e->lp[0].w2 + (long)H * I) - e->lp[0].wqkv;  // wqkv|wo|w1|w2 of one layer are contiguous
-  if (!dlogits) announce(e->p_lm_w, (long)V * H);  // (hidden-state interface: the head's gradient stays zero, its range is complete)
-  AT* gA = BF(p.dA);  // gradient w.r.t. the current layer output = gA (+ gB)
-  AT* gB = nullptr;
+  if (!dlogits) TRY(wq.announce_in_order(e->p_lm_w, (long)V * H));  // (hidden-state interface: the head's gradient stays zero, its range is complete)
+  gA = BF(p.dA);  // gradient w.r.t. the current layer output = gA (+ gB)
+  gB = nullptr;
   if (dhidden)
     SSAK_HIP(hipMemcpyAsync(gA, dhidden, (size_t)M * H * sizeof(AT), hipMemcpyDeviceToDevice, st));
   else {
@@ -1357,210 +1405,136 @@ static int backward_impl(ssak_w2v2* e, const float* dlogits, const void* dhidden
     if (c.final_dropout > 0.f) g.drop(c.final_dropout, DS_FINAL, seed);
     TRY(g.run(st));
   }
-  // ---- encoder layers, last to first.  gA (+gB) = gradient w.r.t. x[l+1], the layer output (post-LN) or the
-  // normalised input of the next layer (stable-LN); Gres = gradient of the residual stream (stable-LN only).
-  const bool stable = whisper || c.do_stable_layer_norm != 0;
-  const AT* Gres = nullptr;
-  auto free_buf = [&](const AT* u1, const AT* u2, const AT* u3) {
-    AT* cand[3] = {BF(p.dC), BF(p.dA), BF(p.scratchH)};
-    for (AT* cnd : cand)
-      if (cnd != u1 && cnd != u2 && cnd != u3) return cnd;
-    return (AT*)nullptr;
-  };
-  WgradQueue wq;
-  // second stages of the layers' column reductions: queued, launched together at every weight-gradient flush
-  ReduceSink sink;
-  struct SinkGuard {
-    SinkGuard(ReduceSink* s) { g_reduce_sink = s; }
-    ~SinkGuard() { g_reduce_sink = nullptr; }
-  };
-  size_t red_used = 0;
-  auto red_take = [&](size_t nfloats) -> float* {  // a partial-sum region that stays untouched until the next flush
-    nfloats = (nfloats + 63) & ~(size_t)63;
-    if (red_used + nfloats > p.redring_floats) return nullptr;
-    float* r = FP(p.redring) + red_used;
-    red_used += nfloats;
-    return r;
-  };
-  auto red_get = [&](size_t nfloats, float** out) -> int {
-    float* r = red_take(nfloats);
-    if (!r) {  // ring full (cannot happen with the flush cadence of two layers; kept for safety): run what is queued
-      TRY(k_reduce_flush(sink, st));
-      red_used = 0;
-      r = red_take(nfloats);
-    }
-    if (!r) {
-      ssak_set_error("w2v2_backward: reduction ring too small");
-      return SSAK_ERR_STATE;
-    }
-    *out = r;
-    return SSAK_OK;
-  };
-  const size_t ln_part_floats = (size_t)LN_BWD_BLOCKS * 3 * H;
-  int kept = 0;  // layers that ran so far: selects the buffer set their weight-gradient operands live in
-  auto flush_reductions = [&]() -> int {
-    TRY(k_reduce_flush(sink, st));
-    red_used = 0;
-    return SSAK_OK;
-  };
-  // Weight-gradient products are packed GREEDILY into launches of at most one round of 256 x 256 tiles (a base layer has 108:
-  // pairs of layers filled 216 of 256 workgroups and LayerDrop left an odd layer over in half of the steps, which then ran as
-  // four split-K launches): a product that does not fit any more starts the next launch, so launches hold ~2.4 layers and a
-  // layer's products may go out in two launches.  Its gradient range is announced when the last of them has been launched.
-  auto flush_gemms = [&]() -> int {
-    TRY(wq.flush(st, slab, p.slab_bytes));
-    int done = 0;
-    while (done < wq.n_ann && wq.ann_last[done] < wq.launched) {
-      announce(wq.ann_off[done], wq.ann_cnt[done]);
-      ++done;
-    }
-    for (int i = done; i < wq.n_ann; ++i) {
-      wq.ann_off[i - done] = wq.ann_off[i];
-      wq.ann_cnt[i - done] = wq.ann_cnt[i];
-      wq.ann_last[i - done] = wq.ann_last[i];
-    }
-    wq.n_ann -= done;
-    return SSAK_OK;
-  };
-  auto wq_push = [&](const Gemm& g, int buffer_set) -> int {
-    const bool full = wq.tiles + WgradQueue::tiles_of(g.d) > 256;
-    if (wq.n > 0 && (full || wq.n == WgradQueue::CAP)) TRY(flush_gemms());
-    wq.push(g, buffer_set);
-    return SSAK_OK;
-  };
-  auto flush_wgrads = [&]() -> int {
-    TRY(flush_reductions());
-    TRY(flush_gemms());
-    return SSAK_OK;
-  };
-  SinkGuard sink_guard(&sink);
   if (dlogits) {
     // lm_head weight gradient: first in the queue, so its range is the first announced (the order every rank agrees on)
     const AT* xl = (c.final_dropout > 0.f) ? BF(p.xf) : BF(e->xin[c.num_layers]);
-    TRY(wq_push(GemmX<EXACT>(V, H, M).a(dlog, V, true).b(xl, H, true).c(Gd + e->p_lm_w, H, true), -1));
-    wq.ann_off[wq.n_ann] = e->p_lm_w;
-    wq.ann_cnt[wq.n_ann] = (long)V * H;
-    wq.ann_last[wq.n_ann++] = wq.pushed - 1;
+    TRY(wq.push(GemmX<EXACT>(V, H, M).a(dlog, V, true).b(xl, H, true).c(Gd + e->p_lm_w, H, true), -1));
+    TRY(wq.announce_after_last_product(e->p_lm_w, (long)V * H));
   }
-  for (int l = c.num_layers - 1; l >= 0; --l) {
-    const LayerP& L = e->lp[l];
-    const LayerBuf& lb = p.lb[l];
-    float* stl = FP(lb.st);
-    float *ln_part = nullptr, *ln_part2 = nullptr, *ffn_part = nullptr, *qkv_part = nullptr;
-    TRY(red_get(ln_part_floats, &ln_part));
-    const long nxt_w = (l + 1 < c.num_layers) ? e->lp[l + 1].ln1w : e->p_eln_w;
-    const long nxt_b = (l + 1 < c.num_layers) ? e->lp[l + 1].ln1b : e->p_eln_b;
-    if (!e->keep[l]) {
-      // zeros (memset above), still part of the all-reduce; behind any kept layer whose gradients are still queued
-      if (wq.n_ann > 0) {
-        wq.ann_off[wq.n_ann] = L.wqkv;
-        wq.ann_cnt[wq.n_ann] = layer_span;
-        wq.ann_last[wq.n_ann++] = -1;
-      } else {
-        announce(L.wqkv, layer_span);
-      }
-      if (!stable) continue;  // identity layer: gradient passes through unchanged
-      // x[l+1] = LN_next(r): its gradient joins the residual-stream gradient; nothing consumed x[l]
-      AT* dr = free_buf(gA, gB, Gres);
-      TRY(k_layernorm_bwd_t<AT>(gA, gB, BF(e->hres[l]), stl + 2 * M, stl + 3 * M, P + nxt_w, Gres, dr, nullptr, Gd + nxt_w, Gd + nxt_b,
-                          ln_part, M, H, none, none, st));
-      Gres = dr;
-      gA = BF(p.dB);
-      gB = nullptr;
-      SSAK_HIP(hipMemsetAsync(gA, 0, (size_t)M * H * sizeof(AT), st));
-      continue;
-    }
-    TRY(red_get(ln_part_floats, &ln_part2));
-    const size_t ffn_part_floats = (size_t)std::max(ssak_cdiv(M, 64), 64) * I;  // (>= 64 rows: the non-fused fallback's partials)
-    TRY(red_get(ffn_part_floats, &ffn_part));
-    // q|k|v bias gradient: first stage inside the fused attention backward kernels when they run, else a column-sum pass over dqkv
-    const size_t qkv_fused_floats = (p.fused_attn && !EXACT) ? k_attention_bwd_bias_floats(B, F, H) : 0;
-    TRY(red_get(std::max((size_t)64 * 3 * H, qkv_fused_floats), &qkv_part));
-    AT* dR = stable ? free_buf(gA, gB, Gres) : BF(p.dC);  // grad wrt r2
-    const int set = kept % WGRAD_SETS;
-    ++kept;
-    if (wq.uses_set(set)) TRY(flush_gemms());  // a queued product still reads the buffers this layer is about to overwrite
-    AT* dY = BF(p.dYb[set]);     // dy of the feed-forward branch (dropout mask applied): dX and dW operand
-    AT* dY1 = BF(p.dY1b[set]);   // dy of the attention branch
-    AT* dI = BF(p.dIb[set]);
-    if (!stable) {
-      // final_layer_norm backward: r2 = x1 + drop(ffn)
-      TRY(k_layernorm_bwd_t<AT>(gA, gB, BF(lb.r2), stl + 2 * M, stl + 3 * M, P + L.ln2w, nullptr, dR, dY,
-                          Gd + L.ln2w, Gd + L.ln2b, ln_part, M, H, DS(c.hidden_dropout, ds_hid2(l)), none, st, none, Gd + L.b2));
-    } else {
-      // (next LN) backward: x[l+1] = LN_next(r2), r2 = r1 + drop(ffn); the residual-stream gradient is added after it
-      TRY(k_layernorm_bwd_t<AT>(gA, gB, BF(lb.r2), stl + 2 * M, stl + 3 * M, P + nxt_w, Gres, dR, dY, Gd + nxt_w,
-                          Gd + nxt_b, ln_part, M, H, DS(c.hidden_dropout, ds_hid2(l)), none, st, none, Gd + L.b2));
-    }
-    // (the dy output is written even without hidden dropout -- a plain copy then -- so that the queued weight-gradient
-    // products always read buffers of this layer's set, never the rotating residual-stream buffers)
-    const AT* dy2 = dY;
-    TRY(wq_push(GemmX<EXACT>(H, I, M).a(dy2, H, true).b(BF(lb.f1), I, true).c(Gd + L.w2, I, true), set));  // (b2's gradient: summed by the LN backward)
-    TRY(GemmX<EXACT>(M, I, H).a(dy2, H).b_wt(EXACT ? nullptr : e->wt(l, 3), H, W + L.w2, I).c(dI, I)
-            .epi(SSAK_EPI_MUL_AUX, BF(lb.f1pre))  // the forward saved the whole factor (GELU' and the dropout mask) as 8-bit codes
-            .drop(c.activation_dropout, ds_act(l), seed)  // (which 1 / (1 - p) the codes decode with; no mask is drawn here)
-            .colsum(Gd + L.b1).run(st, ffn_part, ffn_part_floats * sizeof(float)));  // b1's gradient = column sums of dI, taken in the epilogue
-    TRY(wq_push(GemmX<EXACT>(I, H, M).a(dI, I, true).b(BF(lb.x1), H, true).c(Gd + L.w1, H, true), set));
-    AT* dX = BF(p.dB);
-    TRY(GemmX<EXACT>(M, H, I).a(dI, I).b_wt(EXACT ? nullptr : e->wt(l, 2), I, W + L.w1, H).bfrag(e->wt(l, 2) ? nullptr : e->frag(l, 5)).c(dX, H).run(st));
-    AT* dR1;
-    if (!stable) {
-      // layer_norm backward: r1 = x + drop(attn_out); incoming = dR (residual of r2) + dX
-      dR1 = BF(p.dA);  // gA was consumed by the final_layer_norm backward above
-      TRY(k_layernorm_bwd_t<AT>(dR, dX, BF(lb.r1), stl, stl + M, P + L.ln1w, nullptr, dR1, dY1, Gd + L.ln1w,
-                          Gd + L.ln1b, ln_part2, M, H, DS(c.hidden_dropout, ds_hid1(l)), none, st, none, Gd + L.bo));
-    } else {
-      // final_layer_norm backward: x1 = LN(r1), r1 = r + drop(attn_out); residual gradient dR is added after it
-      dR1 = free_buf(dR, dX, nullptr);
-      TRY(k_layernorm_bwd_t<AT>(dX, nullptr, BF(lb.r1), stl, stl + M, P + L.ln2w, dR, dR1, dY1, Gd + L.ln2w,
-                          Gd + L.ln2b, ln_part2, M, H, DS(c.hidden_dropout, ds_hid1(l)), none, st, none, Gd + L.bo));
-    }
-    const AT* dy1 = dY1;
-    TRY(wq_push(GemmX<EXACT>(H, H, M).a(dy1, H, true).b(BF(lb.ctx), H, true).c(Gd + L.wo, H, true), set));  // (bo's gradient: summed by the LN backward)
-    AT* dctx = free_buf(dR1, dX, nullptr);
-    TRY(GemmX<EXACT>(M, H, H).a(dy1, H).b_wt(EXACT ? nullptr : e->wt(l, 1), H, W + L.wo, H).bfrag(e->wt(l, 1) ? nullptr : e->frag(l, 4)).c(dctx, H).run(st));
-    // attention backward per (utterance, head)
-    AT* qkv = BF(lb.qkv);
-    AT* dqkv = BF(p.dqkvb[set]);
-    const long sq1 = (long)F * 3 * H, sp1 = (long)nh * F * Fp, sp2 = (long)F * Fp, sh1 = (long)F * H;
-    if (p.fused_attn) {
-      if constexpr (!EXACT)
-        TRY(k_attention_bwd(qkv, BF(lb.ctx), FP(lb.lse), flens, dctx, FP(p.delta), dqkv, B, F, nh, H,
-                            DS(c.attention_dropout, ds_attn(l)), e->attn_bwd_mode, st, qkv_fused_floats ? qkv_part : nullptr,
-                            qkv_fused_floats ? Gd + L.bqkv : nullptr));
-    } else {
-      TRY(GemmX<EXACT>(F, hd, F).a(BF(lb.Pd), Fp, true).b(dctx, H, true).c(dqkv + 2 * H, 3 * H)
-              .batch(B, nh, sp1, sp2, sh1, hd, sq1, hd).run(st));  // dV = Pd^T dctx
-      TRY(GemmX<EXACT>(F, F, hd).a(dctx, H).b(qkv + 2 * H, 3 * H).c(BF(p.S), Fp)
-              .batch(B, nh, sh1, hd, sq1, hd, sp1, sp2).run(st));  // dPd = dctx V^T
-      TRY(k_softmax_bwd_t<AT>(BF(p.S), BF(lb.P), BF(p.dSb), B * nh * F, F, Fp, DS(c.attention_dropout, ds_attn(l)), st));
-      TRY(GemmX<EXACT>(F, hd, F).a(BF(p.dSb), Fp).b(qkv + H, 3 * H, true).c(dqkv, 3 * H).alpha(scale)
-              .batch(B, nh, sp1, sp2, sq1, hd, sq1, hd).run(st));  // dQ = scale dS K
-      TRY(GemmX<EXACT>(F, hd, F).a(BF(p.dSb), Fp, true).b(qkv, 3 * H, true).c(dqkv + H, 3 * H).alpha(scale)
-              .batch(B, nh, sp1, sp2, sq1, hd, sq1, hd).run(st));  // dK = scale dS^T Q
-    }
-    TRY(wq_push(GemmX<EXACT>(3 * H, H, M).a(dqkv, 3 * H, true).b(BF(e->xin[l]), H, true).c(Gd + L.wqkv, H, true), set));
-    if (!qkv_fused_floats) TRY(k_colsum_t<AT>(dqkv, 3 * H, M, 3 * H, Gd + L.bqkv, st, qkv_part, (size_t)64 * 3 * H));
-    TRY(GemmX<EXACT>(M, H, 3 * H).a(dqkv, 3 * H).b_wt(EXACT ? nullptr : e->wt(l, 0), 3 * H, W + L.wqkv, H).bfrag(e->wt(l, 0) ? nullptr : e->frag(l, 3)).c(dX, H).run(st));
-    wq.ann_off[wq.n_ann] = L.wqkv;
-    wq.ann_cnt[wq.n_ann] = layer_span;
-    wq.ann_last[wq.n_ann++] = wq.pushed - 1;  // announced once the qkv product -- the layer's last -- has been launched
-    ++wq.layers;
-    if ((wq.layers & 1) == 0) TRY(flush_reductions());  // the deferred second stages of the column reductions go out every two layers
-    if (!stable) {
-      // gradient w.r.t. this layer's input = dR1 (residual of r1) + dX
-      gA = dR1;
-      gB = dX;
-    } else {
-      gA = dX;  // gradient w.r.t. x[l] = LN1_l(residual stream); the stream's own gradient is dR1
-      gB = nullptr;
-      Gres = dR1;
-    }
+  return SSAK_OK;
+}
+
+// ---- a layer LayerDrop skipped in the forward
+template <typename AT>
+int Call<AT>::bwd_dropped_layer(int l, WgradQueue& wq, ReduceRing& red) {
+  float* stl = FP(p.lb[l].st);
+  float* ln_part = nullptr;
+  TRY(red.get((size_t)LN_BWD_BLOCKS * 3 * H, &ln_part));
+  const long nxt_w = next_ln_w(l), nxt_b = next_ln_b(l);
+  // zeros (bwd_zero_grads), still part of the all-reduce; behind any kept layer whose gradients are still queued
+  TRY(wq.announce_in_order(e->lp[l].wqkv, e->layer_span()));
+  if (!stable) return SSAK_OK;  // identity layer: gradient passes through unchanged
+  // x[l+1] = LN_next(r): its gradient joins the residual-stream gradient; nothing consumed x[l]
+  AT* dr = free_buf(gA, gB, Gres);
+  TRY(k_layernorm_bwd_t<AT>(gA, gB, BF(e->hres[l]), stl + 2 * M, stl + 3 * M, P + nxt_w, Gres, dr, nullptr, Gd + nxt_w, Gd + nxt_b,
+                      ln_part, M, H, none, none, st));
+  Gres = dr;
+  gA = BF(p.dB);
+  gB = nullptr;
+  SSAK_HIP(hipMemsetAsync(gA, 0, (size_t)M * H * sizeof(AT), st));
+  return SSAK_OK;
+}
+
+// ---- a layer that ran
+template <typename AT>
+int Call<AT>::bwd_layer(int l, WgradQueue& wq, ReduceRing& red) {
+  const LayerP& L = e->lp[l];
+  const LayerBuf& lb = p.lb[l];
+  float* stl = FP(lb.st);
+  float *ln_part = nullptr, *ln_part2 = nullptr, *ffn_part = nullptr, *qkv_part = nullptr;
+  const size_t ln_part_floats = (size_t)LN_BWD_BLOCKS * 3 * H;
+  TRY(red.get(ln_part_floats, &ln_part));
+  const long nxt_w = next_ln_w(l), nxt_b = next_ln_b(l);
+  TRY(red.get(ln_part_floats, &ln_part2));
+  const size_t ffn_part_floats = (size_t)std::max(ssak_cdiv(M, 64), 64) * I;  // (>= 64 rows: the non-fused fallback's partials)
+  TRY(red.get(ffn_part_floats, &ffn_part));
+  // q|k|v bias gradient: first stage inside the fused attention backward kernels when they run, else a column-sum pass over dqkv
+  const size_t qkv_fused_floats = (p.fused_attn && !EXACT) ? k_attention_bwd_bias_floats(B, F, H) : 0;
+  TRY(red.get(std::max((size_t)64 * 3 * H, qkv_fused_floats), &qkv_part));
+  AT* dR = stable ? free_buf(gA, gB, Gres) : BF(p.dC);  // grad wrt r2
+  const int set = kept % WGRAD_SETS;
+  ++kept;
+  TRY(wq.reserve_set(set));  // a queued product may still read the buffers this layer is about to overwrite
+  AT* dY = BF(p.dYb[set]);     // dy of the feed-forward branch (dropout mask applied): dX and dW operand
+  AT* dY1 = BF(p.dY1b[set]);   // dy of the attention branch
+  AT* dI = BF(p.dIb[set]);
+  if (!stable) {
+    // final_layer_norm backward: r2 = x1 + drop(ffn)
+    TRY(k_layernorm_bwd_t<AT>(gA, gB, BF(lb.r2), stl + 2 * M, stl + 3 * M, P + L.ln2w, nullptr, dR, dY,
+                        Gd + L.ln2w, Gd + L.ln2b, ln_part, M, H, DS(c.hidden_dropout, ds_hid2(l)), none, st, none, Gd + L.b2));
+  } else {
+    // (next LN) backward: x[l+1] = LN_next(r2), r2 = r1 + drop(ffn); the residual-stream gradient is added after it
+    TRY(k_layernorm_bwd_t<AT>(gA, gB, BF(lb.r2), stl + 2 * M, stl + 3 * M, P + nxt_w, Gres, dR, dY, Gd + nxt_w,
+                        Gd + nxt_b, ln_part, M, H, DS(c.hidden_dropout, ds_hid2(l)), none, st, none, Gd + L.b2));
   }
-  TRY(flush_wgrads());
-  g_reduce_sink = nullptr;  // the rest of the backward launches its second stages directly
-  // ---- encoder input
-  AT* dh1 = free_buf(gA, gB, Gres);
+  // (the dy output is written even without hidden dropout -- a plain copy then -- so that the queued weight-gradient
+  // products always read buffers of this layer's set, never the rotating residual-stream buffers)
+  const AT* dy2 = dY;
+  TRY(wq.push(GemmX<EXACT>(H, I, M).a(dy2, H, true).b(BF(lb.f1), I, true).c(Gd + L.w2, I, true), set));  // (b2's gradient: summed by the LN backward)
+  TRY(GemmX<EXACT>(M, I, H).a(dy2, H).b_wt(EXACT ? nullptr : e->wt(l, 3), H, W + L.w2, I).c(dI, I)
+          .epi(SSAK_EPI_MUL_AUX, BF(lb.f1pre))  // the forward saved the whole factor (GELU' and the dropout mask) as 8-bit codes
+          .drop(c.activation_dropout, ds_act(l), seed)  // (which 1 / (1 - p) the codes decode with; no mask is drawn here)
+          .colsum(Gd + L.b1).run(st, ffn_part, ffn_part_floats * sizeof(float)));  // b1's gradient = column sums of dI, taken in the epilogue
+  TRY(wq.push(GemmX<EXACT>(I, H, M).a(dI, I, true).b(BF(lb.x1), H, true).c(Gd + L.w1, H, true), set));
+  AT* dX = BF(p.dB);
+  TRY(GemmX<EXACT>(M, H, I).a(dI, I).b_wt(EXACT ? nullptr : e->wt(l, 2), I, W + L.w1, H).bfrag(e->wt(l, 2) ? nullptr : e->frag(l, 5)).c(dX, H).run(st));
+  AT* dR1;
+  if (!stable) {
+    // layer_norm backward: r1 = x + drop(attn_out); incoming = dR (residual of r2) + dX
+    dR1 = BF(p.dA);  // gA was consumed by the final_layer_norm backward above
+    TRY(k_layernorm_bwd_t<AT>(dR, dX, BF(lb.r1), stl, stl + M, P + L.ln1w, nullptr, dR1, dY1, Gd + L.ln1w,
+                        Gd + L.ln1b, ln_part2, M, H, DS(c.hidden_dropout, ds_hid1(l)), none, st, none, Gd + L.bo));
+  } else {
+    // final_layer_norm backward: x1 = LN(r1), r1 = r + drop(attn_out); residual gradient dR is added after it
+    dR1 = free_buf(dR, dX, nullptr);
+    TRY(k_layernorm_bwd_t<AT>(dX, nullptr, BF(lb.r1), stl, stl + M, P + L.ln2w, dR, dR1, dY1, Gd + L.ln2w,
+                        Gd + L.ln2b, ln_part2, M, H, DS(c.hidden_dropout, ds_hid1(l)), none, st, none, Gd + L.bo));
+  }
+  const AT* dy1 = dY1;
+  TRY(wq.push(GemmX<EXACT>(H, H, M).a(dy1, H, true).b(BF(lb.ctx), H, true).c(Gd + L.wo, H, true), set));  // (bo's gradient: summed by the LN backward)
+  AT* dctx = free_buf(dR1, dX, nullptr);
+  TRY(GemmX<EXACT>(M, H, H).a(dy1, H).b_wt(EXACT ? nullptr : e->wt(l, 1), H, W + L.wo, H).bfrag(e->wt(l, 1) ? nullptr : e->frag(l, 4)).c(dctx, H).run(st));
+  // attention backward per (utterance, head)
+  AT* qkv = BF(lb.qkv);
+  AT* dqkv = BF(p.dqkvb[set]);
+  const long sq1 = (long)F * 3 * H, sp1 = (long)nh * F * Fp, sp2 = (long)F * Fp, sh1 = (long)F * H;
+  if (p.fused_attn) {
+    if constexpr (!EXACT)
+      TRY(k_attention_bwd(qkv, BF(lb.ctx), FP(lb.lse), flens, dctx, FP(p.delta), dqkv, B, F, nh, H,
+                          DS(c.attention_dropout, ds_attn(l)), e->attn_bwd_mode, st, qkv_fused_floats ? qkv_part : nullptr,
+                          qkv_fused_floats ? Gd + L.bqkv : nullptr));
+  } else {
+    TRY(GemmX<EXACT>(F, hd, F).a(BF(lb.Pd), Fp, true).b(dctx, H, true).c(dqkv + 2 * H, 3 * H)
+            .batch(B, nh, sp1, sp2, sh1, hd, sq1, hd).run(st));  // dV = Pd^T dctx
+    TRY(GemmX<EXACT>(F, F, hd).a(dctx, H).b(qkv + 2 * H, 3 * H).c(BF(p.S), Fp)
+            .batch(B, nh, sh1, hd, sq1, hd, sp1, sp2).run(st));  // dPd = dctx V^T
+    TRY(k_softmax_bwd_t<AT>(BF(p.S), BF(lb.P), BF(p.dSb), B * nh * F, F, Fp, DS(c.attention_dropout, ds_attn(l)), st));
+    TRY(GemmX<EXACT>(F, hd, F).a(BF(p.dSb), Fp).b(qkv + H, 3 * H, true).c(dqkv, 3 * H).alpha(scale)
+            .batch(B, nh, sp1, sp2, sq1, hd, sq1, hd).run(st));  // dQ = scale dS K
+    TRY(GemmX<EXACT>(F, hd, F).a(BF(p.dSb), Fp, true).b(qkv, 3 * H, true).c(dqkv + H, 3 * H).alpha(scale)
+            .batch(B, nh, sp1, sp2, sq1, hd, sq1, hd).run(st));  // dK = scale dS^T Q
+  }
+  TRY(wq.push(GemmX<EXACT>(3 * H, H, M).a(dqkv, 3 * H, true).b(BF(e->xin[l]), H, true).c(Gd + L.wqkv, H, true), set));
+  if (!qkv_fused_floats) TRY(k_colsum_t<AT>(dqkv, 3 * H, M, 3 * H, Gd + L.bqkv, st, qkv_part, (size_t)64 * 3 * H));
+  TRY(GemmX<EXACT>(M, H, 3 * H).a(dqkv, 3 * H).b_wt(EXACT ? nullptr : e->wt(l, 0), 3 * H, W + L.wqkv, H).bfrag(e->wt(l, 0) ? nullptr : e->frag(l, 3)).c(dX, H).run(st));
+  TRY(wq.announce_after_last_product(L.wqkv, e->layer_span()));  // (the qkv product is the layer's last)
+  if ((kept & 1) == 0) TRY(red.flush());  // the deferred second stages of the column reductions go out every two kept layers
+  if (!stable) {
+    // gradient w.r.t. this layer's input = dR1 (residual of r1) + dX
+    gA = dR1;
+    gB = dX;
+  } else {
+    gA = dX;  // gradient w.r.t. x[l] = LN1_l(residual stream); the stream's own gradient is dR1
+    gB = nullptr;
+    Gres = dR1;
+  }
+  return SSAK_OK;
+}
+
+// ---- encoder input
+template <typename AT>
+int Call<AT>::bwd_encoder_input(AT** dh1_out) {
+  AT* dh1 = *dh1_out = free_buf(gA, gB, Gres);
   if (!stable) {
     // x0 = drop(LN(h1)), h1 = h0 + gelu(posconv(h0))
     TRY(k_layernorm_bwd_t<AT>(gA, gB, BF(p.h1), FP(p.stE), FP(p.stE) + M, P + e->p_eln_w, nullptr, dh1, nullptr, Gd + e->p_eln_w,
@@ -1570,29 +1544,36 @@ static int backward_impl(ssak_w2v2* e, const float* dlogits, const void* dhidden
     TRY(k_layernorm_bwd_t<AT>(gA, gB, BF(p.h1), FP(p.stE), FP(p.stE) + M, P + e->lp[0].ln1w, Gres, dh1, nullptr, Gd + e->lp[0].ln1w,
                         Gd + e->lp[0].ln1b, FP(p.lnpart), M, H, none, none, st, DS(c.hidden_dropout, DS_ENCIN)));
   }
-  if (whisper) {
-   {
-    // ---- a14 front end backward: r = dropout(gelu(conv2(gelu(conv1(mel)))) + pos); positions are fixed
-    const int NM = c.num_mel_bins, Tin = p.Tin, RS1 = p.RS1, RS2 = p.RS2;
-    AT* dpre2 = BF(p.dY);
-    TRY(k_gelu_grad_mul_t<AT>(dh1, BF(p.wpre2), dpre2, (long)M * H, st));
-    TRY(k_colsum_t<AT>(dpre2, H, M, H, Gd + e->p_c2b, st, FP(p.lnpart), cs_floats));
-    TRY(k_copy_rows_padded_t<AT>(dpre2, BF(p.dpre2pad), B, F, RS2, H, st));
-    // dW2[n][tap*H + c] = sum over rows kk = b*RS2 + t of dy[kk][n] * h1pad[2*kk + tap][c]   (one long-K GEMM)
-    TRY(GemmX<EXACT>(H, 3 * H, B * RS2).a(BF(p.dpre2pad), H, true).b(BF(p.h1pad), 2 * H, true).c(FP(p.dwr), 3 * H, true)
-            .run_wgrad(st, slab, p.slab_bytes));
-    TRY(k_conv_wgrad_unrearrange(FP(p.dwr), Gd + e->p_c2w, H, H, 3, st));
-    // input gradient in column form, then col2im (+ GELU' of conv1's pre-activation)
-    TRY(GemmX<EXACT>(M, 3 * H, H).a(dpre2, H).b(e->conv_w[2], 3 * H, true).c(BF(p.dxcol), 3 * H).run(st));
-    TRY(k_col2im_k3s2_t<AT>(BF(p.dxcol), BF(p.pre1), BF(p.dpre1pad), B, F, Tin, RS1, H, st));
-    TRY(k_colsum_t<AT>(BF(p.dpre1pad), H, B * RS1, H, Gd + e->p_c1b, st, FP(p.lnpart), cs_floats));
-    TRY(GemmX<EXACT>(H, 3 * NM, B * RS1).a(BF(p.dpre1pad), H, true).b(BF(p.melcl), NM, true).c(FP(p.dwr), 3 * NM, true)
-            .run_wgrad(st, slab, p.slab_bytes));
-    TRY(k_conv_wgrad_unrearrange(FP(p.dwr), Gd + e->p_c1w, H, NM, 3, st));
-    for (int l = 0; l < c.num_layers; ++l)  // k_proj has no bias in Whisper: keep its slot out of the optimizer
-      SSAK_HIP(hipMemsetAsync(Gd + e->lp[l].bqkv + H, 0, (size_t)H * sizeof(float), st));
-   }
-  } else {
+  return SSAK_OK;
+}
+
+template <typename AT>
+int Call<AT>::bwd_whisper_frontend(AT* dh1) {
+  // ---- a14 front end backward: r = dropout(gelu(conv2(gelu(conv1(mel)))) + pos); positions are fixed
+  const int NM = c.num_mel_bins, Tin = p.Tin, RS1 = p.RS1, RS2 = p.RS2;
+  AT* dpre2 = BF(p.dY);
+  TRY(k_gelu_grad_mul_t<AT>(dh1, BF(p.wpre2), dpre2, (long)M * H, st));
+  TRY(k_colsum_t<AT>(dpre2, H, M, H, Gd + e->p_c2b, st, FP(p.lnpart), cs_floats));
+  TRY(k_copy_rows_padded_t<AT>(dpre2, BF(p.dpre2pad), B, F, RS2, H, st));
+  // dW2[n][tap*H + c] = sum over rows kk = b*RS2 + t of dy[kk][n] * h1pad[2*kk + tap][c]   (one long-K GEMM)
+  TRY(GemmX<EXACT>(H, 3 * H, B * RS2).a(BF(p.dpre2pad), H, true).b(BF(p.h1pad), 2 * H, true).c(FP(p.dwr), 3 * H, true)
+          .run_wgrad(st, slab, p.slab_bytes));
+  TRY(k_conv_wgrad_unrearrange(FP(p.dwr), Gd + e->p_c2w, H, H, 3, st));
+  // input gradient in column form, then col2im (+ GELU' of conv1's pre-activation)
+  TRY(GemmX<EXACT>(M, 3 * H, H).a(dpre2, H).b(e->conv_w[2], 3 * H, true).c(BF(p.dxcol), 3 * H).run(st));
+  TRY(k_col2im_k3s2_t<AT>(BF(p.dxcol), BF(p.pre1), BF(p.dpre1pad), B, F, Tin, RS1, H, st));
+  TRY(k_colsum_t<AT>(BF(p.dpre1pad), H, B * RS1, H, Gd + e->p_c1b, st, FP(p.lnpart), cs_floats));
+  TRY(GemmX<EXACT>(H, 3 * NM, B * RS1).a(BF(p.dpre1pad), H, true).b(BF(p.melcl), NM, true).c(FP(p.dwr), 3 * NM, true)
+          .run_wgrad(st, slab, p.slab_bytes));
+  TRY(k_conv_wgrad_unrearrange(FP(p.dwr), Gd + e->p_c1w, H, NM, 3, st));
+  for (int l = 0; l < c.num_layers; ++l)  // k_proj has no bias in Whisper: keep its slot out of the optimizer
+    SSAK_HIP(hipMemsetAsync(Gd + e->lp[l].bqkv + H, 0, (size_t)H * sizeof(float), st));
+  return SSAK_OK;
+}
+
+// ---- positional conv, SpecAugment, feature projection and its LayerNorm
+template <typename AT>
+int Call<AT>::bwd_posconv_projection(AT* dh1) {
   AT* dpre = BF(p.dY);
   TRY(k_gelu_grad_mul_t<AT>(dh1, BF(p.pc_pre), dpre, (long)M * H, st));
   TRY(k_colsum_t<AT>(dpre, H, M, H, Gd + e->p_pc_b, st, FP(p.lnpart), cs_floats));
@@ -1651,51 +1632,91 @@ static int backward_impl(ssak_w2v2* e, const float* dlogits, const void* dhidden
   AT* dfeat = p.fe_train ? (((nc - 1) & 1) ? BF(p.fe_db) : BF(p.fe_da)) : BF(p.ln0);  // frozen: scratch, never read
   TRY(k_layernorm_bwd_t<AT>(BF(p.dln0), nullptr, BF(p.feat), FP(p.st0), FP(p.st0) + M, P + e->p_fpln_w, nullptr, dfeat, nullptr,
                       Gd + e->p_fpln_w, Gd + e->p_fpln_b, FP(p.lnpart), M, C, none, none, st));
-  if (p.fe_train) {
-    const bool ln_fe = c.feat_extract_norm == 1;
-    // ---- a3 backward (--no_freeze): conv stack in reverse.  Per layer: GELU', weight gradient as per-utterance
-    // K-major GEMMs on the overlapping-row operand (slabs summed in a fixed order), input gradient in column form
-    // (one GEMM) + col2im; finally conv0 + GroupNorm + GELU backward by recomputation from the waveform.
-    for (int i = nc - 1; i >= 1; --i) {
-      const int Ci = c.conv_dim[i - 1], Co = c.conv_dim[i], k = c.conv_kernel[i], s = c.conv_stride[i];
-      const int Ti = p.Tl[i], Tp = p.Tl[i - 1];
-      const AT* dact = (i & 1) ? BF(p.fe_db) : BF(p.fe_da);
-      AT* dprev = ((i - 1) & 1) ? BF(p.fe_db) : BF(p.fe_da);
-      const AT* act_prev = BF(p.act[i - 1]);
-      if (ln_fe) {
-        // layer-norm variant: act = gelu(LN(conv + bias)); one kernel takes d act through GELU' and the LayerNorm
-        // (recomputed from the kept pre-LN values + statistics) and sums d gamma / d beta and the conv bias gradient
-        TRY(k_layernorm_bwd_t<AT>(dact, nullptr, BF(p.cpre[i]), FP(p.fe_st[i]), FP(p.fe_st[i]) + (size_t)B * Ti, P + e->p_cln_w[i], nullptr,
-                            BF(p.fe_dp), BF(p.fe_dp), Gd + e->p_cln_w[i], Gd + e->p_cln_b[i], FP(p.lnpart), B * Ti, Co, none, none, st, none,
-                            c.conv_bias ? Gd + e->p_conv_b[i] : nullptr, P + e->p_cln_b[i]));
-      } else {
-        TRY(k_gelu_grad_mul_t<AT>(dact, BF(p.cpre[i]), BF(p.fe_dp), (long)B * Ti * Co, st));
-      }
-      TRY(GemmX<EXACT>(Co, k * Ci, Ti).a(BF(p.fe_dp), Co, true).b(act_prev, (long)s * Ci, true).c(FP(p.fe_slab), (long)k * Ci, true)
-              .batch(B, 1, (long)Ti * Co, 0, (long)Tp * Ci, 0, (long)Co * k * Ci, 0).run(st));
-      TRY(k_sum_slabs(FP(p.fe_slab), B, (long)Co * k * Ci, FP(p.fe_dwr), st));
-      TRY(k_conv_wgrad_unrearrange(FP(p.fe_dwr), Gd + e->p_conv_w[i], Co, Ci, k, st));
-      TRY(GemmX<EXACT>(Ti, k * Ci, Co).a(BF(p.fe_dp), Co).b(e->conv_w[i], (long)k * Ci, true).c(BF(p.fe_dxcol), (long)k * Ci)
-              .batch(B, 1, (long)Ti * Co, 0, 0, 0, (long)Ti * k * Ci, 0).run(st));
-      TRY(k_col2im_t<AT>(BF(p.fe_dxcol), dprev, B, Tp, Ti, Ci, k, s, st));
-    }
+  return SSAK_OK;
+}
+
+template <typename AT>
+int Call<AT>::bwd_feature_encoder() {
+  const bool ln_fe = c.feat_extract_norm == 1;
+  // ---- a3 backward (--no_freeze): conv stack in reverse.  Per layer: GELU', weight gradient as per-utterance
+  // K-major GEMMs on the overlapping-row operand (slabs summed in a fixed order), input gradient in column form
+  // (one GEMM) + col2im; finally conv0 + GroupNorm + GELU backward by recomputation from the waveform.
+  for (int i = nc - 1; i >= 1; --i) {
+    const int Ci = c.conv_dim[i - 1], Co = c.conv_dim[i], k = c.conv_kernel[i], s = c.conv_stride[i];
+    const int Ti = p.Tl[i], Tp = p.Tl[i - 1];
+    const AT* dact = (i & 1) ? BF(p.fe_db) : BF(p.fe_da);
+    AT* dprev = ((i - 1) & 1) ? BF(p.fe_db) : BF(p.fe_da);
+    const AT* act_prev = BF(p.act[i - 1]);
     if (ln_fe) {
-      const int C0 = c.conv_dim[0], T0 = p.Tl[0];
-      TRY(k_layernorm_bwd_t<AT>(BF(p.fe_da), nullptr, BF(p.cpre[0]), FP(p.fe_st[0]), FP(p.fe_st[0]) + (size_t)B * T0, P + e->p_cln_w[0], nullptr,
-                          BF(p.fe_dp), BF(p.fe_dp), Gd + e->p_cln_w[0], Gd + e->p_cln_b[0], FP(p.lnpart), B * T0, C0, none, none, st, none,
-                          c.conv_bias ? Gd + e->p_conv_b[0] : nullptr, P + e->p_cln_b[0]));
-      TRY(k_conv0_wgrad_t<AT>(BF(p.fe_dp), e->last_input, Gd + e->p_conv_w[0], FP(p.fe_c0), B, p.T, T0, C0, c.conv_kernel[0],
-                        c.conv_stride[0], st));
+      // layer-norm variant: act = gelu(LN(conv + bias)); one kernel takes d act through GELU' and the LayerNorm
+      // (recomputed from the kept pre-LN values + statistics) and sums d gamma / d beta and the conv bias gradient
+      TRY(k_layernorm_bwd_t<AT>(dact, nullptr, BF(p.cpre[i]), FP(p.fe_st[i]), FP(p.fe_st[i]) + (size_t)B * Ti, P + e->p_cln_w[i], nullptr,
+                          BF(p.fe_dp), BF(p.fe_dp), Gd + e->p_cln_w[i], Gd + e->p_cln_b[i], FP(p.lnpart), B * Ti, Co, none, none, st, none,
+                          c.conv_bias ? Gd + e->p_conv_b[i] : nullptr, P + e->p_cln_b[i]));
     } else {
-      TRY(k_conv0_gn_gelu_bwd_t<AT>(e->last_input, P + e->p_conv_w[0], P + e->p_cln_w[0], P + e->p_cln_b[0], BF(p.fe_da),
-                              (const double*)(ws + p.stats0), FP(p.fe_c0), Gd + e->p_conv_w[0], Gd + e->p_cln_w[0],
-                              Gd + e->p_cln_b[0], B, p.T, p.Tl[0], c.conv_dim[0], st));
+      TRY(k_gelu_grad_mul_t<AT>(dact, BF(p.cpre[i]), BF(p.fe_dp), (long)B * Ti * Co, st));
     }
+    TRY(GemmX<EXACT>(Co, k * Ci, Ti).a(BF(p.fe_dp), Co, true).b(act_prev, (long)s * Ci, true).c(FP(p.fe_slab), (long)k * Ci, true)
+            .batch(B, 1, (long)Ti * Co, 0, (long)Tp * Ci, 0, (long)Co * k * Ci, 0).run(st));
+    TRY(k_sum_slabs(FP(p.fe_slab), B, (long)Co * k * Ci, FP(p.fe_dwr), st));
+    TRY(k_conv_wgrad_unrearrange(FP(p.fe_dwr), Gd + e->p_conv_w[i], Co, Ci, k, st));
+    TRY(GemmX<EXACT>(Ti, k * Ci, Co).a(BF(p.fe_dp), Co).b(e->conv_w[i], (long)k * Ci, true).c(BF(p.fe_dxcol), (long)k * Ci)
+            .batch(B, 1, (long)Ti * Co, 0, 0, 0, (long)Ti * k * Ci, 0).run(st));
+    TRY(k_col2im_t<AT>(BF(p.fe_dxcol), dprev, B, Tp, Ti, Ci, k, s, st));
   }
+  if (ln_fe) {
+    const int C0 = c.conv_dim[0], T0 = p.Tl[0];
+    TRY(k_layernorm_bwd_t<AT>(BF(p.fe_da), nullptr, BF(p.cpre[0]), FP(p.fe_st[0]), FP(p.fe_st[0]) + (size_t)B * T0, P + e->p_cln_w[0], nullptr,
+                        BF(p.fe_dp), BF(p.fe_dp), Gd + e->p_cln_w[0], Gd + e->p_cln_b[0], FP(p.lnpart), B * T0, C0, none, none, st, none,
+                        c.conv_bias ? Gd + e->p_conv_b[0] : nullptr, P + e->p_cln_b[0]));
+    TRY(k_conv0_wgrad_t<AT>(BF(p.fe_dp), e->last_input, Gd + e->p_conv_w[0], FP(p.fe_c0), B, p.T, T0, C0, c.conv_kernel[0],
+                      c.conv_stride[0], st));
+  } else {
+    TRY(k_conv0_gn_gelu_bwd_t<AT>(e->last_input, P + e->p_conv_w[0], P + e->p_cln_w[0], P + e->p_cln_b[0], BF(p.fe_da),
+                            (const double*)(ws + p.stats0), FP(p.fe_c0), Gd + e->p_conv_w[0], Gd + e->p_cln_w[0],
+                            Gd + e->p_cln_b[0], B, p.T, p.Tl[0], c.conv_dim[0], st));
+  }
+  return SSAK_OK;
+}
+
+// dlogits (after ssak_w2v2_forward) or dhidden (after ssak_w2v2_forward_hidden): exactly one is non-null
+template <typename AT>
+static int backward_impl(ssak_w2v2* e, const float* dlogits, const void* dhidden /*AT [M, H]*/, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  SSAK_REQUIRE(e && (dlogits || dhidden) && workspace, "w2v2_backward: null pointer");
+  SSAK_REQUIRE(e->cfg.adapter_attn_dim == 0,
+               "w2v2_backward: a model with language adapters (adapter_attn_dim > 0) runs inference only: training is not implemented");
+  if (!e->have_fwd || e->fwd_hidden != (dhidden != nullptr)) {
+    ssak_set_error("w2v2_backward: no matching training-mode forward to differentiate");
+    return SSAK_ERR_STATE;
+  }
+  EngineCall engine_call(e);
+  SSAK_REQUIRE(e->G, "w2v2_backward: no gradient buffer bound");
+  SSAK_REQUIRE(workspace_bytes >= e->plan.total, "w2v2_backward: workspace too small");
+  Call<AT> k(e, workspace, stream, true);
+  TRY(k.bwd_zero_grads());
+  WgradQueue wq(e, k.st, k.slab, k.p.slab_bytes);
+  TRY(k.bwd_head(dlogits, dhidden, wq));
+  {
+    // encoder layers, last to first; the second stages of their column reductions are queued in the ring's sink and launched
+    // together every two kept layers and with the last weight gradients
+    ReduceRing red(k.FP(k.p.redring), k.p.redring_floats, k.st);
+    for (int l = e->cfg.num_layers - 1; l >= 0; --l) TRY(e->keep[l] ? k.bwd_layer(l, wq, red) : k.bwd_dropped_layer(l, wq, red));
+    TRY(red.flush());
+    TRY(wq.flush());
+  }
+  AT* dh1 = nullptr;
+  TRY(k.bwd_encoder_input(&dh1));
+  if (k.whisper) {
+    TRY(k.bwd_whisper_frontend(dh1));
+  } else {
+    TRY(k.bwd_posconv_projection(dh1));
+    if (k.p.fe_train) TRY(k.bwd_feature_encoder());
   }
   // everything else: the leading small matrices and the whole vector region (biases, LayerNorm affine)
-  announce(0, e->lp[0].wqkv);
-  announce(e->p_lm_w + (long)V * H, n_grad - (e->p_lm_w + (long)V * H));
+  const long vectors = e->p_lm_w + (long)k.V * k.H;
+  k.announce(0, e->lp[0].wqkv);
+  k.announce(vectors, e->n_grad() - vectors);
   e->have_fwd = false;
   return SSAK_OK;
 }

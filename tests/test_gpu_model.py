@@ -284,6 +284,45 @@ def test_trainer_bucketed_allreduce_single_rank(mods):
     assert per_step == Wav2Vec2ForCTC.grad_ranges(_cfg_from_oracle(Wav2Vec2Config, oc))
 
 
+@pytest.mark.parametrize("stable", [False, True])
+@pytest.mark.parametrize("pattern", ["all_dropped", "only_last_kept"])
+def test_layerdrop_at_the_layer_limit_announces_every_range_in_order(mods, stable, pattern):
+    """64 layers (the most the engine takes) with every layer dropped, or only layer 63 kept: the head's range and then every
+    layer's wait in the announcement queue at once (65 entries).  The announced sequence is still the static one, dropped
+    layers have exactly zero gradients, and the step is bitwise repeatable."""
+    Wav2Vec2Config, Wav2Vec2ForCTC, R = mods
+    L = 64
+    kw = dict(feat_extract_norm="layer", conv_bias=True, do_stable_layer_norm=True) if stable else {}
+    oc = R.W2V2Config.tiny(num_hidden_layers=L, **kw)
+    cfg = _cfg_from_oracle(Wav2Vec2Config, oc)
+    rng = np.random.default_rng(1)
+    x = torch.tensor(R.zero_mean_unit_var_norm([rng.standard_normal(8000).astype(np.float32) for _ in range(2)]))
+    labels = torch.tensor(R.pad_labels([[3, 4, 5], [6, 7]]))
+    keep = [pattern == "only_last_kept" and l == L - 1 for l in range(L)]
+    model = Wav2Vec2ForCTC(cfg, seed=11).train()
+    model.load_state_dict(R.init_params(oc, 3))
+    ranges = Wav2Vec2ForCTC.grad_ranges(cfg)
+    assert len(ranges) == L + 3  # head, the layers, the leading matrices, the vectors
+    # (SpecAugment spans and the dropout seed are the caller's, so that the second step is the first one again)
+    mask = R.compute_mask_indices((2, model.num_frames(8000)), 0.2, 3, None, 2, rng=np.random.RandomState(3))
+    steps = []
+    for _ in range(2):
+        seen = []
+        model.set_grad_ready_callback(lambda o, c: seen.append((o, c)))
+        out = model(x, labels=labels, mask_time_indices=mask, layer_keep=keep, dropout_seed=7)
+        model.grads[:model.num_trainable].fill_(float("nan"))  # an earlier step's values must be overwritten or zeroed, never kept
+        model.backward()
+        assert seen == ranges
+        assert np.isfinite(out.loss.item())
+        steps.append(model.grads[:model.num_trainable].clone())
+    assert torch.equal(steps[0], steps[1])
+    assert bool(torch.isfinite(steps[0]).all())
+    for l in range(L):  # ranges[1 + (L - 1 - l)] = the four matrices (q|k|v, out, ffn up, ffn down) of layer l
+        off, cnt = ranges[1 + (L - 1 - l)]
+        nonzero = bool((steps[0][off:off + cnt] != 0).any())
+        assert nonzero == keep[l], (l, nonzero)
+
+
 def test_whisper_encoder_ctc_vs_hf(gold):
     """BASELINE config 4 composition (WhisperEncoder -> Linear -> CTC; no reference call site): tiny
     dimensions, log-mel features computed by the HIP front end (a13) from the waveform, against the golden made with
