@@ -597,8 +597,8 @@ int ssak_augment_gain_noise(const float* x, const int32_t* lens, const int32_t* 
 /* Reverberation (rows of kind REVERB; every other row is copied).  augment_reverberation.py:104-177: h truncated to its first
  * L samples, rotated by its peak d (d >= L: not rotated), circular convolution of length L, then
  * y = w / (mean|w| + 1e-14) * mean|x|.  Computed as a linear convolution through one complex FFT of x + i h of
- * N = 2^k >= L + min(Lh, L) - 1 points (four-step, N <= 2^24), folded modulo L.  x and y may alias.
- * workspace >= ssak_augment_reverb_workspace_bytes(B, T, longest RIR). */
+ * N = 2^k >= L + min(Lh, L) - 1 points (four-step, N <= 2^24), folded modulo L.  An all-zero x or h[:L] gives y = 0 exactly.
+ * x and y may alias.  workspace >= ssak_augment_reverb_workspace_bytes(B, T, longest RIR). */
 size_t ssak_augment_reverb_workspace_bytes(int B, int T, int max_rir_len);
 int ssak_augment_reverb(const float* x, const int32_t* lens, const int32_t* lens_host /*host*/, int B, int T, const double* params,
                         const double* params_host /*host*/, const ssak_audio_bank* rirs /*host struct; may be NULL without REVERB rows*/,
