@@ -953,12 +953,9 @@ int k_attention_bwd(const bf16* qkv, const bf16* ctx, const float* lse, const in
 #undef ATT_LAUNCH_DKV
   SSAK_LAUNCH_CHECK();
   if (bias_part) {
-    // second stage: with the caller's queued reductions (ReduceSink) when there is one, else here
-    const int slots = B * ssak_cdiv(F, 64 * TILE);
-    if (!(g_reduce_sink && g_reduce_sink->push(bias_part, 3L * H, slots, 3 * H, bias_grad))) {
-      const int rc = k_colsum_rows(bias_part, slots, 3 * H, bias_grad, st);
-      if (rc != SSAK_OK) return rc;
-    }
+    // second stage: with the caller's queued reductions (ReduceSink) when there is one, else here, timed as a row-wise helper
+    const ReduceJob job{bias_part, bias_grad, 3L * H, B * ssak_cdiv(F, 64 * TILE), 3 * H};
+    return k_reduce(&job, 1, st, PROF_ROWWISE);
   }
   return SSAK_OK;
 }

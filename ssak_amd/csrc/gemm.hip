@@ -682,26 +682,6 @@ int dispatch_layout(const GemmParams& p, int a_km, int b_km, bool dma, hipStream
   return launch<BM, BN, WM, WN, true, false, NJ>(p, dma, st);
 }
 
-
-// out[n] += sum over slots of partial[slot][n], fixed order (the column sums the epilogues left per wave-tile row).
-// Workgroup = 64 columns x 16 slot groups; the groups are combined in LDS in a fixed order.
-__global__ __launch_bounds__(1024) void colsum_slots_kernel(const float* __restrict__ partial, int slots, int N, float* __restrict__ out) {
-  __shared__ float red[16][65];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int n = blockIdx.x * 64 + cx;
-  float s = 0.f;
-  if (n < N)
-    for (int k = ry; k < slots; k += 16) s += partial[(long)k * N + n];
-  red[ry][cx] = s;
-  __syncthreads();
-  if (ry == 0 && n < N) {
-    float t = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t += red[r][cx];
-    out[n] += t;
-  }
-}
-
 // ---- kernel / tile / split-K selection ---------------------------------------------------------------------------
 // A small cost model in microseconds (constants fitted to tools/bench_gemm.py and tools/probes/p8_probe.hip on the
 // Wav2Vec2-base train-step shapes, MI355X): a workgroup costs a fixed prologue + epilogue plus a per-K-tile time, the
@@ -954,10 +934,9 @@ extern "C" int ssak_gemm_bf16(const ssak_gemm_desc* d, const void* A, const void
   }
   if (colsum_out) {
     if (colsum_fused) {
-      const int slots = 2 * ssak_cdiv(d->M, p8_bm);  // (tile row, wave row) pairs, wave tiles of p8_bm / 2 rows
-      if (g_reduce_sink && g_reduce_sink->push((const float*)workspace, d->N, slots, d->N, colsum_out)) return SSAK_OK;
-      colsum_slots_kernel<<<ssak_cdiv(d->N, 64), 1024, 0, st>>>((const float*)workspace, slots, d->N, colsum_out);
-      SSAK_LAUNCH_CHECK();
+      // the column sums the epilogues left per (tile row, wave row) pair, wave tiles of p8_bm / 2 rows
+      const ReduceJob job{(const float*)workspace, colsum_out, d->N, 2 * ssak_cdiv(d->M, p8_bm), d->N};
+      return k_reduce(&job, 1, st);
     } else {
       // separate pass over the stored C; two-stage and fixed-order when the workspace can hold its partial rows
       // (min(64, ceil(M / 32)) * N floats), float atomics otherwise

@@ -40,6 +40,10 @@ struct DropSpec {
 // launch -- 50 per train step, a fifth of all launches.  While a sink is installed (the engine's backward does, per pair of
 // encoder layers) the producers queue the job instead and k_reduce_flush runs all of them as ONE launch; the partial buffers
 // must stay untouched until then.
+// reduce_jobs_kernel (norm_act.hip) is the one kernel of this shape.  The remaining second stages are other sums: the
+// positional convolution's posconv_colnorm_finalize_kernel (conv_frontend.hip) ASSIGNS its total; the slab sums of the
+// --no_freeze feature-encoder backward (sum_slabs_kernel, conv0_wgrad_sum_kernel, conv0_bwd_dw_kernel) add sequentially and
+// sb_head.hip totals in double precision, so their bits would change under this summation order.
 struct ReduceJob {
   const float* partial;
   float* out;
@@ -50,13 +54,12 @@ struct ReduceSink {
   static constexpr int CAP = 32;
   ReduceJob jobs[CAP];
   int n = 0;
-  bool push(const float* partial, long stride, int slots, int ncols, float* out) {
-    if (n >= CAP) return false;
-    jobs[n++] = ReduceJob{partial, out, stride, slots, ncols};
-    return true;
-  }
 };
 extern thread_local ReduceSink* g_reduce_sink;
+// The second stage of ONE producer call: all n jobs are queued when a sink is installed and has room for them, else all run
+// now (a call is never half queued).  prof_slot >= 0: a launch made here is timed under that slot -- for a caller that does not
+// already hold a row-wise scope of its own; a queued job is timed by the flush.
+int k_reduce(const ReduceJob* jobs, int n, hipStream_t st, int prof_slot = -1);
 int k_reduce_flush(ReduceSink& sink, hipStream_t st);
 
 // norm_act.hip -- row / element-wise kernels, templates over the activation storage type T (bf16: production engine,
@@ -164,7 +167,6 @@ size_t k_attention_bwd_bias_floats(int B, int F, int H);
 int k_attention_bwd(const bf16* qkv, const bf16* ctx, const float* lse, const int32_t* klens, const bf16* dctx, float* delta,
                     bf16* dqkv, int B, int F, int nh, int H, const DropSpec& drop, int mode /* SSAK_ATTN_BWD_* */, hipStream_t st,
                     float* bias_part = nullptr, float* bias_grad = nullptr);
-int k_colsum_rows(const float* partial, int slots, int N, float* out, hipStream_t st);  // out[n] += sum over slots of partial[slot][n]
 
 // posconv.hip: the grouped positional convolution as a direct convolution (input window resident in LDS)
 bool k_posconv_direct_supported(int H, int G, int K);

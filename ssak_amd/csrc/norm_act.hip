@@ -258,7 +258,7 @@ struct LnBwdParams {
   const T* g_res;     // [M,C] extra gradient added to dr AFTER the LN backward (pre-LN residual stream) or null
   T* dr;              // [M,C] grad wrt r (residual path)
   T* dy;              // [M,C] grad wrt y = dr * premask/(1-p)  (null when no pre-dropout: use dr)
-  float* dgamma;      // [C] += (finalize kernel)
+  float* dgamma;      // [C] += (the second stage, k_reduce)
   float* dbeta;
   float* partial;     // [gridDim.x][3][C] per-workgroup column partials
   float* dy_colsum;   // [C] += column sums of dy (the bias gradient of the Linear that produced the branch) or null
@@ -449,33 +449,9 @@ __global__ __launch_bounds__(ROW_THREADS) void ln_bwd_kernel(const LnBwdParams<T
   }
 }
 
-__global__ __launch_bounds__(1024) void ln_bwd_finalize_kernel(const float* __restrict__ partial, int nblk, int C,
-                                                               float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                               float* __restrict__ dy_colsum) {
-  // workgroup = 64 columns x 16 row groups; fixed summation order (deterministic), then one += per column
-  __shared__ float red[16][65];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int e = blockIdx.x * 64 + cx;  // index into [3][C] (the third plane only when dy_colsum is given)
-  const int planes = dy_colsum ? 3 : 2;
-  float s = 0.f;
-  if (e < planes * C) {
-    const int which = e / C, col = e % C;
-#pragma unroll 8
-    for (int b = ry; b < nblk; b += 16) s += partial[((size_t)b * 3 + which) * C + col];
-  }
-  red[ry][cx] = s;
-  __syncthreads();
-  if (ry == 0 && e < planes * C) {
-    float t = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t += red[r][cx];
-    const int which = e / C, col = e % C;
-    float* dst = which == 0 ? dgamma : which == 1 ? dbeta : dy_colsum;
-    dst[col] += t;
-  }
-}
-
-// All queued second stages in one launch.  Workgroup = 64 columns x 16 slot groups of one job (fixed summation order).
+// The second stage of every two-stage column sum (kernels.h: ReduceJob), a table of jobs per launch.  Workgroup = 64 columns x
+// 16 slot groups of one job: group ry adds slots ry, ry + 16, ... in order, then the 16 group sums are added in order (fixed
+// summation order: deterministic), one += per column.
 struct ReduceTable {
   ReduceJob jobs[ReduceSink::CAP];
   int first_block[ReduceSink::CAP + 1];
@@ -510,6 +486,32 @@ __global__ __launch_bounds__(1024) void reduce_jobs_kernel(const ReduceTable t) 
     for (int r = 0; r < 16; ++r) v += red[r][cx];
     q.out[n] += v;
   }
+}
+int reduce_launch(const ReduceJob* jobs, int n /* <= ReduceSink::CAP */, hipStream_t st) {
+  for (int done = 0; done < n;) {
+    // jobs that add into the same vector must not share a launch (plain +=): cut the batch at the first repeat
+    ReduceTable t;
+    t.n = 0;
+    int blocks = 0;
+    for (int i = done; i < n; ++i) {
+      bool repeat = false;
+      for (int k = 0; k < t.n; ++k) repeat |= t.jobs[k].out == jobs[i].out;
+      if (repeat) break;
+      t.first_block[t.n] = blocks;
+      t.jobs[t.n++] = jobs[i];
+      blocks += ssak_cdiv(jobs[i].ncols, 64);
+    }
+    t.first_block[t.n] = blocks;
+    reduce_jobs_kernel<<<blocks, 1024, 0, st>>>(t);
+    SSAK_LAUNCH_CHECK();
+    done += t.n;
+  }
+  return SSAK_OK;
+}
+double reduce_bytes(const ReduceJob* jobs, int n) {
+  double bytes = 0.0;
+  for (int i = 0; i < n; ++i) bytes += (double)jobs[i].slots * jobs[i].ncols * 4.0;
+  return bytes;
 }
 
 // ---------------------------------------------------------------------------------------------- softmax
@@ -675,23 +677,6 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ X, lo
       else
         atomicAdd(out + c, s);
     }
-  }
-}
-// out[n] += sum over `slots` rows of partial [slots][N], fixed order; workgroup = 64 columns x 16 slot groups
-__global__ __launch_bounds__(1024) void colsum_rows_kernel(const float* __restrict__ partial, int slots, int N, float* __restrict__ out) {
-  __shared__ float red[16][65];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int n = blockIdx.x * 64 + cx;
-  float s = 0.f;
-  if (n < N)
-    for (int k = ry; k < slots; k += 16) s += partial[(long)k * N + n];
-  red[ry][cx] = s;
-  __syncthreads();
-  if (ry == 0 && n < N) {
-    float t = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t += red[r][cx];
-    out[n] += t;
   }
 }
 
@@ -876,15 +861,12 @@ int k_layernorm_bwd_t(const T* g1, const T* g2, const T* r, const float* mean, c
 #undef LN_BWD_LAUNCH
   SSAK_LAUNCH_CHECK();
 launched:
-  if (g_reduce_sink && g_reduce_sink->n + 3 <= ReduceSink::CAP) {  // second stage queued: one launch for many (kernels.h)
-    g_reduce_sink->push(partial, 3L * C, grid, C, dgamma);
-    g_reduce_sink->push(partial + C, 3L * C, grid, C, dbeta);
-    if (dy_colsum) g_reduce_sink->push(partial + 2 * C, 3L * C, grid, C, dy_colsum);
-    return SSAK_OK;
-  }
-  ln_bwd_finalize_kernel<<<ssak_cdiv((dy_colsum ? 3 : 2) * C, 64), 1024, 0, st>>>(partial, grid, C, dgamma, dbeta, dy_colsum);
-  SSAK_LAUNCH_CHECK();
-  return SSAK_OK;
+  // second stage: the planes of the [grid][3][C] partials, queued or launched together (kernels.h).  A sink is asked for room
+  // for the 2 or 3 jobs pushed; it used to be asked for 3 either way, which differs only at exactly CAP - 2 queued jobs, a
+  // fill the engine's flush cadence does not reach.
+  const ReduceJob jobs[3] = {{partial, dgamma, 3L * C, grid, C}, {partial + C, dbeta, 3L * C, grid, C},
+                             {partial + 2 * C, dy_colsum, 3L * C, grid, C}};
+  return k_reduce(jobs, dy_colsum ? 3 : 2, st);
 }
 
 template <typename T>
@@ -934,48 +916,30 @@ int k_colsum_t(const T* X, long ld, int M, int N, float* out, hipStream_t st, fl
   const bool det = scratch && scratch_floats >= (size_t)grid.y * N;  // deterministic two-stage sum when a scratch is given
   colsum_kernel<T><<<grid, 256, 0, st>>>(X, ld, M, N, out, det ? scratch : nullptr, rowmask, flens, F > 0 ? F : 1);
   SSAK_LAUNCH_CHECK();
-  if (det) {
-    if (g_reduce_sink && g_reduce_sink->push(scratch, N, (int)grid.y, N, out)) return SSAK_OK;
-    colsum_rows_kernel<<<ssak_cdiv(N, 64), 1024, 0, st>>>(scratch, (int)grid.y, N, out);
-    SSAK_LAUNCH_CHECK();
-  }
-  return SSAK_OK;
+  if (!det) return SSAK_OK;
+  const ReduceJob job{scratch, out, N, (int)grid.y, N};
+  return k_reduce(&job, 1, st);
 }
 
 thread_local ReduceSink* g_reduce_sink = nullptr;
 
-int k_colsum_rows(const float* partial, int slots, int N, float* out, hipStream_t st) {
-  ProfScope prof_scope(PROF_ROWWISE, (double)slots * N * 4.0, st);
-  colsum_rows_kernel<<<ssak_cdiv(N, 64), 1024, 0, st>>>(partial, slots, N, out);
-  SSAK_LAUNCH_CHECK();
-  return SSAK_OK;
+int k_reduce(const ReduceJob* jobs, int n, hipStream_t st, int prof_slot) {
+  SSAK_REQUIRE(jobs && n > 0 && n <= ReduceSink::CAP, "reduce: %d jobs in one call (1 .. %d)", n, ReduceSink::CAP);
+  if (ReduceSink* const sink = g_reduce_sink; sink && sink->n + n <= ReduceSink::CAP) {
+    std::copy(jobs, jobs + n, sink->jobs + sink->n);
+    sink->n += n;
+    return SSAK_OK;
+  }
+  if (prof_slot < 0) return reduce_launch(jobs, n, st);
+  ProfScope prof_scope(prof_slot, reduce_bytes(jobs, n), st);
+  return reduce_launch(jobs, n, st);
 }
 
 int k_reduce_flush(ReduceSink& sink, hipStream_t st) {
-  int done = 0;
-  double bytes = 0.0;
-  for (int i = 0; i < sink.n; ++i) bytes += (double)sink.jobs[i].slots * sink.jobs[i].ncols * 4.0;
-  ProfScope prof_scope(PROF_ROWWISE, bytes, st);
-  while (done < sink.n) {
-    // jobs that add into the same vector must not share a launch (plain +=): cut the batch at the first repeat
-    ReduceTable t;
-    t.n = 0;
-    int blocks = 0;
-    for (int i = done; i < sink.n; ++i) {
-      bool repeat = false;
-      for (int k = 0; k < t.n; ++k) repeat |= t.jobs[k].out == sink.jobs[i].out;
-      if (repeat) break;
-      t.first_block[t.n] = blocks;
-      t.jobs[t.n++] = sink.jobs[i];
-      blocks += ssak_cdiv(sink.jobs[i].ncols, 64);
-    }
-    t.first_block[t.n] = blocks;
-    reduce_jobs_kernel<<<blocks, 1024, 0, st>>>(t);
-    SSAK_LAUNCH_CHECK();
-    done += t.n;
-  }
+  ProfScope prof_scope(PROF_ROWWISE, reduce_bytes(sink.jobs, sink.n), st);
+  const int rc = reduce_launch(sink.jobs, sink.n, st);
   sink.n = 0;
-  return SSAK_OK;
+  return rc;
 }
 
 int k_cast_f32_bf16(const float* in, bf16* out, long n, hipStream_t st) {

@@ -18,8 +18,9 @@ NCH = ceil(C / 512), or ln_bwd_kernel<T, NCH, VEC, PGELU, DROP> with (NCH, VEC) 
   (3, 4) at 768 -- each with DROP = false (no site), DROP = true (every site, g2, g_res, dy) and PGELU (with and without
   dropout): test_ln_bwd_generic.  bf16 (3, 4) / (2, 8) at 768 / 1024 with DROP = false are never launched (every bit set without
   dropout is specialised there); with DROP they are reached by SP = 63.
-* ln_bwd_finalize_kernel and the queued reduce_jobs_kernel: every backward case (alternating), bit-identical to each other in
-  test_ln_bwd_deterministic.
+* reduce_jobs_kernel, launched directly by k_reduce and from the queue by k_reduce_flush: every backward case (alternating), the
+  two bit-identical to each other in test_ln_bwd_deterministic; the bound of its unrolled loop (241, 256, 257 partial rows) and a
+  partly filled column block (C = 72), on both paths: test_ln_bwd_reduce_unroll_edges.
 * softmax_fwd_kernel / softmax_bwd_kernel<T, 1 | 2 | 3> (ld <= 512, <= 1024, <= 1536), both T: test_softmax.
 
 Data: every 7 rows cycle through a constant row (its output must be beta), a row of std ~3e-3 (variance near eps = 1e-5),
@@ -48,7 +49,8 @@ Bars (u = 2^-24, the fp32 unit roundoff; eps_st = 2^-8 for bf16 storage -- half 
 * GELU over [-12, 12] (clamp points +-6 and their neighbours included): bf16 fit |gelu - x Phi(x)| <= 1.65e-5 |x| + 2^-22 |gelu|
   and |gelu' - (Phi(x) + x phi(x))| <= 1.65e-5 + 2^-20, and within 1e-6 of the float64 restatement of the fit; fp32 (erff) within
   1e-6 |x| and 1e-6.
-* Two launches are bit-identical, and so are the queued and the direct column sums (same summation order).
+* Two launches are bit-identical, and so are the queued and the direct column sums (reduce_jobs_kernel either way: the same
+  summation order, whatever else shares the launch).
 """
 import os
 import sys
@@ -342,8 +344,8 @@ def test_ln_bwd_rows(case, M):
 
 @pytest.mark.parametrize("case", ["bf16-spec51-C1024", "bf16-spec36-C768", "bf16-generic-C512", "fp32-C1536"])
 def test_ln_bwd_deterministic(case):
-    """Two launches are bit-identical, and the queued second stage (ReduceSink + reduce_jobs_kernel, the engine's path) equals
-    ln_bwd_finalize_kernel bit for bit."""
+    """Two launches are bit-identical, and the queued second stage (ReduceSink + k_reduce_flush, the engine's path) equals the
+    direct launch of reduce_jobs_kernel bit for bit."""
     if case.startswith("fp32"):
         a, b, c = run_ln_bwd(F32, 6000, 1536, pre=0.1, mid=0.1, post=0.1, repeat=True)
     elif "generic" in case:
@@ -355,6 +357,20 @@ def test_ln_bwd_deterministic(case):
         if a[k] is not None:
             assert np.array_equal(a[k], b[k]), f"{k}: two launches differ"
             assert np.array_equal(a[k], c[k]), f"{k}: queued and direct second stages differ"
+
+
+@pytest.mark.parametrize("C", [64, 72])
+@pytest.mark.parametrize("M", [964, 1024, 1028])
+def test_ln_bwd_reduce_unroll_edges(M, C):
+    """The second stage's sixteen-loads-in-flight loop runs while k + 240 < slots, k = ry, ry + 256, ...: M = 964, 1024, 1028 rows
+    are 241, 256, 257 partial rows -- at 241 only slot group 0 enters the unrolled loop, 256 and 257 sit either side of its tail
+    (at 257 group 0 has one slot left over for the scalar loop).  C = 72: the second column block holds 8 of its 64 columns.
+    Against the reference with the usual bars, and direct against queued bit for bit."""
+    a, b, c = run_ln_bwd(BF, M, C, pre=0.1, rng_seed=M + C, repeat=True)
+    for k in a:
+        assert a[k] is not None, k
+        assert np.array_equal(a[k], b[k]), f"{k}: two launches differ"
+        assert np.array_equal(a[k], c[k]), f"{k}: queued and direct second stages differ"
 
 
 # ------------------------------------------------------------------------------------------------ softmax
