@@ -777,6 +777,25 @@ int ssak_dec_timestamp_step(const float* logits, long ldv, int B, int V, const u
                             int ts_begin, int no_timestamps_id, int max_initial, const void* embed_tokens, const void* embed_positions, int D,
                             int max_positions, int next_pos, int eos_id, int pad_id, uint8_t* finished, int32_t* n_unfinished,
                             int32_t* tokens, float* logprobs, long ldt, int t, int32_t* ts_last, void* h_next, void* stream);
+/* ---- Whisper sampling (ABI 640): the token selection of a step at temperature > 0 ------------------------------------------
+ * ssak_dec_sample_step.  ssak_dec_timestamp_step's arguments, outputs and conventions, plus `temperature` and `seed`; ts_last == NULL
+ * means no timestamp rules (ssak_dec_greedy_step's filters; ts_begin, no_timestamps_id and max_initial are not read).  The row is
+ * filtered as those two entries filter it, the mass rule included, which fixes the candidate set: the allowed timestamp columns
+ * alone when the timestamps' mass wins, else every allowed column (whisper sets logits[:, :timestamp_begin] = -inf before
+ * Categorical(logits = logits / T).sample()).  token = the LOWEST column that attains the maximum of
+ *     x_c * (1 / T) + g_c,   g_c = -log(-log(u_c))
+ * over the set: g_c is a Gumbel variate, so the arg-max is one exact draw from softmax(x / T) over the set.  u_c depends on (seed, t,
+ * row, c) through hash_u32 alone:
+ *     k = hash_u32(seed, 0x5A0, (uint64(t) << 32) | row),   w = hash_u32(seed ^ (uint64(k) << 32), 0x5A1, c),
+ *     u = ((w >> 9) + 0.5) * 2^-23   (strictly inside (0, 1), exact in fp32; g lies in [-2.81, 16.64]).
+ * A column with x_c = -inf never wins.  logprob = (x_token - M) - log(S over the candidate set), the log-softmax of the UNTEMPERED
+ * processed row.  A finished row draws nothing and emits pad_id with log-prob 0, as does a row with no allowed column.  Two calls
+ * with the same arguments give the same bits.  temperature <= 0, NaN, or with a reciprocal that overflows fp32, and everything
+ * ssak_dec_greedy_step refuses (with ts_last: everything ssak_dec_timestamp_step refuses): SSAK_ERR_INVALID, nothing launched. */
+int ssak_dec_sample_step(const float* logits, long ldv, int B, int V, const uint8_t* suppress, const uint8_t* begin_suppress, int first,
+                         int ts_begin, int no_timestamps_id, int max_initial, const void* embed_tokens, const void* embed_positions, int D,
+                         int max_positions, int next_pos, int eos_id, int pad_id, uint8_t* finished, int32_t* n_unfinished, int32_t* tokens,
+                         float* logprobs, long ldt, int t, int32_t* ts_last, void* h_next, float temperature, uint64_t seed, void* stream);
 /* ---- Whisper beam search (ABI 630): nb hypotheses per audio, R = B * nb rows, K = nb + 1 candidates per row ----------------
  * What whisper/decoding.py BeamSearchDecoder does per step, on the device, with the conventions of ABI 610 / 620: no host mirrors,
  * nothing read back, fp32 sums in a fixed order, integer atomics only; a refusal returns SSAK_ERR_INVALID and launches nothing.

@@ -17,7 +17,7 @@
 // ssak_dec_attention_step_grouped) query row b reads the keys and klens of utterance b / group: the beams of an audio share its
 // cross k|v buffer.
 //
-// dec_token_step_kernel<VEC, TS>.  One workgroup per row, the two-pass shape of token_logprobs_kernel with the suppress masks applied
+// dec_token_step_kernel<VEC, TS, SAMPLE>.  One workgroup per row, the two-pass shape of token_logprobs_kernel with the suppress masks applied
 // as the columns are read (whisper_step.h: scan_allowed, the loop dec_beam_topk_kernel runs).  Without TS it is the greedy step
 // (ABI 610): one running maximum with its lowest column, one sum; the rules' type is NoRules and nothing of them is compiled in.
 // With TS (ABI 620) whisper's ApplyTimestampRules are folded into the column predicate.  The rules of a row reduce to uniform
@@ -25,7 +25,11 @@
 // one text interval [text_lo, ts_begin) and one timestamp interval [ts_lo, ts_hi]; a column is allowed when no mask byte hits it,
 // it is not <|notimestamps|> and it lies in one of the two.  No per-row mask exists in memory.  Pass one carries four running
 // statistics per thread (the text and the timestamp maximum, each with its lowest column), pass two the two sums of exp(x - M)
-// in column order; lanes, then waves, in a fixed order.
+// in column order; lanes, then waves, in a fixed order.  With SAMPLE (ABI 640, ssak_dec_sample_step; with or without TS) passes one
+// and two are the same and the mass decision fixes the candidate set instead of the token -- the timestamp columns alone when the
+// mass wins, else every allowed column; a third scan takes the arg-max of x_c / T + g_c over that set, g_c = -log(-log(u_c)) a
+// Gumbel variate of the counter-based uniform sample_uniform (whisper_step.h), which is one exact draw from softmax(x / T) over
+// the set with no prefix sum in it; the log-probability is the drawn column's under the UNTEMPERED processed row.
 #include <limits.h>
 
 #include <algorithm>
@@ -210,9 +214,11 @@ struct GsParams {
   int V, D, t, next_pos, eos_id, pad_id;
   int32_t* ts_last;  // (this line and the next: read with TS only)
   int ts_begin, no_timestamps_id, max_initial;
+  float inv_temperature;  // (this line and the next: read with SAMPLE only)
+  uint64_t seed;
 };
 
-template <bool VEC, bool TS>
+template <bool VEC, bool TS, bool SAMPLE = false>
 __global__ __launch_bounds__(GS_THREADS) void dec_token_step_kernel(const GsParams p) {
   __shared__ float red[16];
   __shared__ int32_t ired[16];
@@ -253,7 +259,25 @@ __global__ __launch_bounds__(GS_THREADS) void dec_token_step_kernel(const GsPara
       });
       st = block_sum(st, red);
       if constexpr (TS) ss = block_sum(ss, red);
-      if (TS && ts_mass_wins(ss, mt, M)) {
+      if constexpr (SAMPLE) {
+        // pass three: the arg-max of x / T + Gumbel noise over the candidate set the mass decision fixed (a -inf column's score
+        // is -inf and never beats the initial -inf; the lowest column on a tie)
+        const bool only_ts = TS && ts_mass_wins(ss, mt, M);
+        const uint64_t rowseed = sample_rowseed(p.seed, p.t, row);
+        const float inv_t = p.inv_temperature;
+        float best = -INFINITY;
+        int32_t bi = INT_MAX;
+        scan_allowed<VEC>(x, p.suppress, p.begin_suppress, V, rules, [&](int c, float v) {
+          const float sc = v * inv_t - logf(-logf(sample_uniform(rowseed, c)));
+          const bool b = (!TS || !only_ts || c >= tsb) && sc > best;
+          best = b ? sc : best, bi = b ? c : bi;
+        });
+        block_argmax(best, bi, red, ired);
+        if (bi < V) {
+          token = bi;
+          logprob = (x[bi] - M) - logf(only_ts ? ss : st + ss);
+        }
+      } else if (TS && ts_mass_wins(ss, mt, M)) {
         token = is;
         logprob = (ms - M) - logf(ss);
       } else {
@@ -333,7 +357,7 @@ extern "C" int ssak_dec_attention_step(const void* q, long ldq, const void* k, l
 }
 
 namespace {
-// what ssak_dec_greedy_step and ssak_dec_timestamp_step refuse alike; fills the shared parameters
+// what ssak_dec_greedy_step, ssak_dec_timestamp_step and ssak_dec_sample_step refuse alike; fills the shared parameters
 int greedy_params(const char* who, const float* logits, long ldv, int B, int V, const uint8_t* suppress, const uint8_t* begin_suppress, int first,
                   const void* embed_tokens, const void* embed_positions, int D, int max_positions, int next_pos, int eos_id, int pad_id,
                   uint8_t* finished, int32_t* n_unfinished, int32_t* tokens, float* logprobs, long ldt, int t, void* h_next, GsParams* out) {
@@ -348,17 +372,27 @@ int greedy_params(const char* who, const float* logits, long ldv, int B, int V, 
   p.finished = finished, p.n_unfinished = n_unfinished, p.tokens = tokens, p.logprobs = logprobs, p.h_next = (bf16*)h_next;
   p.ldv = ldv, p.ldt = ldt, p.V = V, p.D = D, p.t = t, p.next_pos = next_pos, p.eos_id = eos_id, p.pad_id = pad_id;
   p.ts_last = nullptr, p.ts_begin = p.no_timestamps_id = 0, p.max_initial = -1;
+  p.inv_temperature = 0.f, p.seed = 0;
+  return SSAK_OK;
+}
+// what the entries that apply the timestamp rules refuse alike; fills the rules' parameters
+int ts_params(const char* who, int ts_begin, int no_timestamps_id, int max_initial, int eos_id, int V, int32_t* ts_last, GsParams* out) {
+  SSAK_REQUIRE(ts_last, "%s: ts_last is NULL", who);
+  SSAK_REQUIRE(ts_begin > eos_id && ts_begin < V, "%s: ts_begin=%d must lie in (eos_id=%d, V=%d)", who, ts_begin, eos_id, V);
+  SSAK_REQUIRE(no_timestamps_id >= 0 && no_timestamps_id < V, "%s: no_timestamps_id=%d outside [0, %d)", who, no_timestamps_id, V);
+  GsParams& p = *out;
+  p.ts_last = ts_last, p.ts_begin = ts_begin, p.no_timestamps_id = no_timestamps_id, p.max_initial = max_initial < 0 ? -1 : max_initial;
   return SSAK_OK;
 }
 // the count zeroed, then the one kernel on B rows
-template <bool TS>
+template <bool TS, bool SAMPLE = false>
 int launch_token_step(const GsParams& p, int B, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   SSAK_HIP(hipMemsetAsync(p.n_unfinished, 0, sizeof(int32_t), st));
   if (scan_vec(p.logits, p.ldv, p.suppress, p.begin_suppress))
-    dec_token_step_kernel<true, TS><<<B, GS_THREADS, 0, st>>>(p);
+    dec_token_step_kernel<true, TS, SAMPLE><<<B, GS_THREADS, 0, st>>>(p);
   else
-    dec_token_step_kernel<false, TS><<<B, GS_THREADS, 0, st>>>(p);
+    dec_token_step_kernel<false, TS, SAMPLE><<<B, GS_THREADS, 0, st>>>(p);
   SSAK_LAUNCH_CHECK();
   return SSAK_OK;
 }
@@ -383,9 +417,26 @@ extern "C" int ssak_dec_timestamp_step(const float* logits, long ldv, int B, int
   const int rc = greedy_params("dec_timestamp_step", logits, ldv, B, V, suppress, begin_suppress, first, embed_tokens, embed_positions, D,
                                max_positions, next_pos, eos_id, pad_id, finished, n_unfinished, tokens, logprobs, ldt, t, h_next, &p);
   if (rc != SSAK_OK) return rc;
-  SSAK_REQUIRE(ts_last, "dec_timestamp_step: ts_last is NULL");
-  SSAK_REQUIRE(ts_begin > eos_id && ts_begin < V, "dec_timestamp_step: ts_begin=%d must lie in (eos_id=%d, V=%d)", ts_begin, eos_id, V);
-  SSAK_REQUIRE(no_timestamps_id >= 0 && no_timestamps_id < V, "dec_timestamp_step: no_timestamps_id=%d outside [0, %d)", no_timestamps_id, V);
-  p.ts_last = ts_last, p.ts_begin = ts_begin, p.no_timestamps_id = no_timestamps_id, p.max_initial = max_initial < 0 ? -1 : max_initial;
+  if (const int rt = ts_params("dec_timestamp_step", ts_begin, no_timestamps_id, max_initial, eos_id, V, ts_last, &p)) return rt;
   return launch_token_step<true>(p, B, stream);
+}
+
+extern "C" int ssak_dec_sample_step(const float* logits, long ldv, int B, int V, const uint8_t* suppress, const uint8_t* begin_suppress, int first,
+                                    int ts_begin, int no_timestamps_id, int max_initial, const void* embed_tokens, const void* embed_positions,
+                                    int D, int max_positions, int next_pos, int eos_id, int pad_id, uint8_t* finished, int32_t* n_unfinished,
+                                    int32_t* tokens, float* logprobs, long ldt, int t, int32_t* ts_last, void* h_next, float temperature,
+                                    uint64_t seed, void* stream) {
+  GsParams p;
+  const int rc = greedy_params("dec_sample_step", logits, ldv, B, V, suppress, begin_suppress, first, embed_tokens, embed_positions, D, max_positions,
+                               next_pos, eos_id, pad_id, finished, n_unfinished, tokens, logprobs, ldt, t, h_next, &p);
+  if (rc != SSAK_OK) return rc;
+  // (NaN fails the first comparison; a temperature whose reciprocal overflows fp32 would turn every score into inf)
+  SSAK_REQUIRE(temperature > 0.f && 1.f / temperature < INFINITY,
+               "dec_sample_step: temperature=%g must be positive with a finite reciprocal (temperature 0 is ssak_dec_greedy_step / "
+               "ssak_dec_timestamp_step)",
+               (double)temperature);
+  p.inv_temperature = 1.f / temperature, p.seed = seed;
+  if (!ts_last) return launch_token_step<false, true>(p, B, stream);  // no rules: the timestamp arguments are not read
+  if (const int rt = ts_params("dec_sample_step", ts_begin, no_timestamps_id, max_initial, eos_id, V, ts_last, &p)) return rt;
+  return launch_token_step<true, true>(p, B, stream);
 }

@@ -64,6 +64,19 @@ inline bool scan_vec(const float* logits, long ldv, const uint8_t* s0, const uin
 // the timestamps' mass against the likeliest text token: log S_ts - log S > m_text - M - log S, with ss = S_ts / exp(M)
 __device__ __forceinline__ bool ts_mass_wins(float ss, float mt, float M) { return ss > 0.f && logf(ss) > mt - M; }
 
+// The uniform of the sampling step (ssak_dec_sample_step), from hash_u32 alone: a key per (seed, step t, row), a word per column
+// under a seed whose high half carries that key, and the word's top 23 bits at the centre of their cell: u = (2 k + 1) 2^-24 with
+// k in [0, 2^23), strictly inside (0, 1) and exact in fp32.  (Not the rank-one rowkey * colmul word of the dropout masks: there
+// two rows' words are multiples of each other.)
+constexpr uint32_t DS_SAMPLE = 0x5A0u;
+__device__ __forceinline__ uint64_t sample_rowseed(uint64_t seed, int t, int row) {
+  const uint32_t k = hash_u32(seed, DS_SAMPLE, ((uint64_t)(uint32_t)t << 32) | (uint32_t)row);
+  return seed ^ ((uint64_t)k << 32);
+}
+__device__ __forceinline__ float sample_uniform(uint64_t rowseed, int c) {
+  return ((float)(hash_u32(rowseed, DS_SAMPLE + 1, (uint64_t)(uint32_t)c) >> 9) + 0.5f) * 0x1p-23f;
+}
+
 // (value, lowest column) of the maximum over the workgroup: lanes, then waves; every thread returns the same pair
 __device__ __forceinline__ void block_argmax(float& best, int32_t& bi, float* red, int32_t* ired) {
 #pragma unroll

@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 630  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 640  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -184,6 +184,8 @@ def _load():
         "ssak_dec_greedy_step": (i32, [vp, C.c_long, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_long, i32, vp, vp]),
         "ssak_dec_timestamp_step": (i32, [vp, C.c_long, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_long,
                                           i32, vp, vp, vp]),
+        "ssak_dec_sample_step": (i32, [vp, C.c_long, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_long,
+                                       i32, vp, vp, f32, C.c_uint64, vp]),
         "ssak_dec_beam_topk": (i32, [vp, C.c_long, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, C.c_long, i32, vp, vp, i32, vp, vp, vp]),
         "ssak_dec_beam_select": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, C.c_long, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32,
                                        i32, i32, i32, i32, vp, vp]),
@@ -839,6 +841,19 @@ def dec_timestamp_step(logits, V: int, *, finished, n_unfinished, tokens, logpro
                                  embed_tokens, embed_positions, next_pos, h_next)
     assert ts_last is None or (ts_last.is_cuda and ts_last.dtype == torch.int32 and ts_last.numel() == logits.shape[0] and ts_last.is_contiguous())
     check(lib.ssak_dec_timestamp_step(*head, int(ts_begin), int(no_timestamps_id), int(max_initial), *mid, ptr(ts_last), ptr(h_next), stream()))
+
+
+def dec_sample_step(logits, V: int, *, finished, n_unfinished, tokens, logprobs, t: int, eos_id: int, pad_id: int, temperature: float, seed: int,
+                    ts_begin: int = 0, no_timestamps_id: int = 0, ts_last=None, max_initial: int = -1, suppress=None, begin_suppress=None,
+                    first: bool = False, embed_tokens=None, embed_positions=None, next_pos: int = 0, h_next=None):
+    """``ssak_dec_sample_step`` (ABI 640): :func:`dec_timestamp_step` (``ts_last=None``: :func:`dec_greedy_step`, no rules) drawing the
+    token from ``softmax(x / temperature)`` over the filtered row instead of taking its maximum; the log-probability is the drawn
+    token's under the untempered row.  The draw is a function of ``(seed, t, row, column)``: the same call gives the same bits."""
+    head, mid = _token_step_args(logits, V, finished, n_unfinished, tokens, logprobs, t, eos_id, pad_id, suppress, begin_suppress, first,
+                                 embed_tokens, embed_positions, next_pos, h_next)
+    assert ts_last is None or (ts_last.is_cuda and ts_last.dtype == torch.int32 and ts_last.numel() == logits.shape[0] and ts_last.is_contiguous())
+    check(lib.ssak_dec_sample_step(*head, int(ts_begin), int(no_timestamps_id), int(max_initial), *mid, ptr(ts_last), ptr(h_next),
+                                   float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, stream()))
 
 
 # ------------------------------------------------------------------ Whisper beam search (ABI 630): nb hypotheses per audio, R = B * nb rows

@@ -34,11 +34,15 @@ files of any length by the timestamps it predicted, as ``model.transcribe`` does
 
 Token ids are the contract (no tokenizer is needed, and none is shipped); :meth:`WhisperSeq2Seq.score_text` is a convenience
 that imports ``transformers.WhisperTokenizer`` lazily.  Beam search (``generate(beam_size=N)``, the reference's ``--beam_size`` / ``--accurate``): ``ssak_dec_beam_topk`` /
-``ssak_dec_beam_select`` / ``ssak_dec_kv_reorder`` keep N hypotheses per utterance on the device.  Not built: fallback temperatures,
-sampling, ``best_of``, a beam ``patience`` and ``compression_ratio_threshold``, ``condition_on_previous_text`` / ``initial_prompt``, word timestamps, a skinny-M GEMM for the token step, hipGraph capture
+``ssak_dec_beam_select`` / ``ssak_dec_kv_reorder`` keep N hypotheses per utterance on the device.  Sampling (``generate(temperature=T,
+best_of=N, seed=s)``): ``ssak_dec_sample_step`` draws each token from the filtered distribution, N candidates per utterance ranked on
+the host; the temperature fallback on ``compression_ratio_threshold`` / ``logprob_threshold`` is the host loop of
+ssak_amd/whisper_transcribe.py (DESIGN.md "Whisper sampling and temperature fallback").  Not built: a beam ``patience``,
+``condition_on_previous_text`` / ``initial_prompt``, word timestamps, a skinny-M GEMM for the token step, hipGraph capture
 of the step, training / LoRA, an fp32-exact mode of the decoder.  Timing: tools/bench_whisper_decoder.py,
-tools/bench_whisper_generate.py, tools/bench_whisper_transcribe.py, tools/bench_whisper_beam.py (DESIGN.md "Whisper decoder",
-"Whisper generation", "Whisper long-form transcription", "Whisper beam search").
+tools/bench_whisper_generate.py, tools/bench_whisper_transcribe.py, tools/bench_whisper_beam.py, tools/bench_whisper_sample.py
+(DESIGN.md "Whisper decoder", "Whisper generation", "Whisper long-form transcription", "Whisper beam search", "Whisper sampling and
+temperature fallback").
 """
 from __future__ import annotations
 
@@ -133,7 +137,9 @@ class GenerateResult:
     ``<|startoftranscript|>`` row.  ``beams`` (only with ``beam_size``, else None): per utterance the ``beam_size`` candidates
     ``(tokens, sum_logprob)`` in finalisation order -- the finished sequences in the order they finished, then the live ones by
     descending sum; the other fields describe the candidate the ranking chose, ``sum_logprob`` being the device's fp32 running sum;
-    ``beam_logprobs``: per utterance and candidate the per-token log-probs (float64 arrays, as long as the candidate's tokens)."""
+    ``beam_logprobs``: per utterance and candidate the per-token log-probs (float64 arrays, as long as the candidate's tokens).
+    ``samples`` (only with ``temperature > 0``, else None): per utterance the ``best_of`` drawn candidates ``(tokens, sum_logprob)`` in
+    row order, ``sample_logprobs`` their per-token log-probs; the other fields describe the candidate the ranking chose."""
     tokens: List[List[int]]
     lens: np.ndarray
     token_array: np.ndarray
@@ -144,6 +150,8 @@ class GenerateResult:
     no_speech_prob: Optional[np.ndarray] = None
     beams: Optional[list] = None
     beam_logprobs: Optional[list] = None
+    samples: Optional[list] = None
+    sample_logprobs: Optional[list] = None
 
 
 # The shortest self-attention cache on which the token step runs ssak_dec_attention_step; below it, ssak_dec_attention_fwd at
@@ -233,6 +241,14 @@ def beam_rank(cands, length_penalty=None) -> int:
         n = len(toks) - 1 if fin else len(toks)
         scores.append(-np.inf if n == 0 else s / (n if length_penalty is None else ((5 + n) / 6) ** length_penalty))
     return int(np.argmax(scores))
+
+
+def sample_call_seed(seed: int) -> int:
+    """The 64-bit seed ``ssak_dec_sample_step`` gets for a :meth:`WhisperSeq2Seq.generate` call with ``seed``: state 0 from
+    ``np.random.SeedSequence(seed)``, then one 64-bit LCG step, as :class:`ssak_amd.model.Wav2Vec2ForCTC` derives its dropout seeds.
+    Within the call the kernel's draws differ by step and row."""
+    s = int(np.random.SeedSequence(int(seed)).generate_state(1, dtype=np.uint64)[0])
+    return (s * 6364136223846793005 + 1442695040888963407) % (1 << 64)
 
 
 def _decoder_layout(cfg: WhisperSeq2SeqConfig):
@@ -788,8 +804,10 @@ class WhisperSeq2Seq:
 
     def generate(self, enc_or_audio, prompt=None, language=None, task: str = "transcribe", max_new_tokens: Optional[int] = None, enc_lens=None,
                  suppress_tokens=None, begin_suppress_tokens=None, eos_token_id: Optional[int] = None, poll_every: int = 8,
-                 timestamps: bool = False, beam_size: Optional[int] = None, length_penalty: Optional[float] = None) -> GenerateResult:
-        """Greedy transcription (temperature 0), or beam search with ``beam_size``, of a batch in lock step -> :class:`GenerateResult`.
+                 timestamps: bool = False, beam_size: Optional[int] = None, length_penalty: Optional[float] = None, temperature: float = 0.0,
+                 best_of: Optional[int] = None, seed: int = 1234) -> GenerateResult:
+        """Greedy transcription (temperature 0), beam search with ``beam_size``, or sampling with ``temperature > 0``, of a batch in lock
+        step -> :class:`GenerateResult`.
 
         ``prompt`` [B, P] or [P] ids (one P for the batch); by default ``[<|startoftranscript|>, language, task,
         <|notimestamps|>]``, where ``language = None`` runs :meth:`detect_language`'s pass first (on this call's cross k|v buffer) and gives each
@@ -809,19 +827,36 @@ class WhisperSeq2Seq:
         ``min(max_target_positions // 2, max_target_positions - P)`` tokens (whisper's ``sample_len``), and ``no_speech_prob``
         in the result.  The default leaves the call as it was.
 
-        ``beam_size`` in [1, 8]: whisper's ``BeamSearchDecoder`` (DESIGN.md "Whisper beam search": no patience, no temperature
-        fallback) with ``MaximumLikelihoodRanker(length_penalty)``.  The prompt, the language pass and ``no_speech_prob`` run once
+        ``beam_size`` in [1, 8]: whisper's ``BeamSearchDecoder`` (DESIGN.md "Whisper beam search": no patience) with ``MaximumLikelihoodRanker(length_penalty)``.  The prompt, the language pass and ``no_speech_prob`` run once
         per utterance; the token step runs ``B * beam_size`` rows whose cross-attention shares the utterance's one cross k|v buffer;
         the self-attention cache follows the hypotheses (``ssak_dec_kv_reorder``).  ``GenerateResult.beams`` lists every candidate.
-        ``beam_size=None`` is the greedy path, unchanged."""
+        ``beam_size=None`` is the greedy path, unchanged.
+
+        ``temperature > 0``: every token is drawn from ``softmax(x / temperature)`` over the filtered row (``ssak_dec_sample_step``,
+        DESIGN.md "Whisper sampling and temperature fallback"), with and without ``timestamps``.  ``best_of`` in [1, 8] (None: 1)
+        draws that many candidates per utterance -- the prompt runs once per utterance, the rows of an utterance share its cross k|v
+        buffer as beams do and differ by their row index in the draw -- and ``MaximumLikelihoodRanker(length_penalty)`` picks one;
+        ``GenerateResult.samples`` lists them all.  The same ``seed`` gives the same result.  ``beam_size`` together with
+        ``temperature > 0`` is refused (whisper drops the beam there; :func:`ssak_amd.whisper_transcribe.transcribe` does the
+        dropping).  ``temperature = 0`` (the default) leaves the call as it was and ignores ``best_of`` and ``seed``."""
         cfg = self.config
         timestamps = bool(timestamps)
+        temperature = float(temperature)
+        if not temperature >= 0.0 or temperature == float("inf"):
+            raise ValueError(f"temperature {temperature}: a finite value >= 0 is expected")
+        n_samp = 0  # decoder rows per utterance when sampling; 0: not sampling
+        if temperature > 0.0:
+            if beam_size is not None:
+                raise ValueError("beam_size with temperature > 0: whisper samples there instead of searching; pass best_of")
+            n_samp = 1 if best_of is None else int(best_of)
+            if not 1 <= n_samp <= 8:
+                raise ValueError(f"best_of {best_of}: 1 to 8 candidates per utterance are built")
         if beam_size is not None:
             beam_size = int(beam_size)
             if not 1 <= beam_size <= 8:
                 raise ValueError(f"beam_size {beam_size}: 1 to 8 hypotheses per utterance are built")
-        elif length_penalty is not None:
-            raise ValueError("length_penalty ranks the candidates of a beam search: pass beam_size")
+        elif length_penalty is not None and not n_samp:
+            raise ValueError("length_penalty ranks the candidates of a beam search or of best_of samples: pass beam_size, or temperature and best_of")
         if timestamps and cfg.no_timestamps_token_id is None:
             raise ValueError("timestamps=True: the model folder names no no_timestamps_token_id (generation_config.json), the timestamp ids are "
                              "those above it")
@@ -829,6 +864,8 @@ class WhisperSeq2Seq:
         B = enc.shape[0]
         if beam_size is not None and B * beam_size > 65535:
             raise ValueError(f"{B} utterances x beam_size {beam_size} = {B * beam_size} decoder rows: at most 65535 in one call")
+        if B * n_samp > 65535:
+            raise ValueError(f"{B} utterances x best_of {n_samp} = {B * n_samp} decoder rows: at most 65535 in one call")
         V, maxp = cfg.vocab_size, cfg.max_target_positions
         eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
         if eos is None:
@@ -856,7 +893,7 @@ class WhisperSeq2Seq:
             raise ValueError("poll_every must be >= 0")
         sup = self._token_mask(cfg.suppress_tokens if suppress_tokens is None else suppress_tokens, "suppress_tokens")
         bsup = self._token_mask(cfg.begin_suppress_tokens if begin_suppress_tokens is None else begin_suppress_tokens, "begin_suppress_tokens")
-        st = self._gen_begin(enc, enc_lens, cap=P + n_max, group=1 if beam_size is None else beam_size)
+        st = self._gen_begin(enc, enc_lens, cap=P + n_max, group=max(n_samp, 1) if beam_size is None else beam_size)
         if detect:
             prompt = self.default_prompt(B, self._detect_language(enc, st.enc_lens_host, cross_kv=st.cross_kv)[0], task, timestamps)
         no_speech = None
@@ -877,17 +914,23 @@ class WhisperSeq2Seq:
             ts = dict(ts_begin=ts_begin, no_timestamps_id=int(cfg.no_timestamps_token_id), max_initial=max_initial) if timestamps else None
             return self._generate_beam(st, logits, P, n_max, eos, pad, sup, bsup, ts, poll_every, length_penalty, no_speech)
         E, Pz = self._w("embed_tokens.weight"), self._w("embed_positions.weight")
+        R = B * st.group  # the step's rows: one per utterance, best_of per utterance when sampling
         with torch.cuda.device(self.device):
-            tokens = torch.full((B, n_max), pad, dtype=torch.int32, device=self.device)
-            logprobs = torch.zeros((B, n_max), dtype=torch.float32, device=self.device)
-            finished = torch.zeros(B, dtype=torch.uint8, device=self.device)
+            tokens = torch.full((R, n_max), pad, dtype=torch.int32, device=self.device)
+            logprobs = torch.zeros((R, n_max), dtype=torch.float32, device=self.device)
+            finished = torch.zeros(R, dtype=torch.uint8, device=self.device)
             n_unf = torch.zeros(1, dtype=torch.int32, device=self.device)
-            h_next = torch.empty((B, st.D), dtype=torch.bfloat16, device=self.device)
+            h_next = torch.empty((R, st.D), dtype=torch.bfloat16, device=self.device)
             step, rules = hip.dec_greedy_step, {}
             if timestamps:
                 step = hip.dec_timestamp_step
                 rules = dict(ts_begin=ts_begin, no_timestamps_id=cfg.no_timestamps_token_id, max_initial=max_initial,
-                             ts_last=torch.full((B,), -1, dtype=torch.int32, device=self.device))
+                             ts_last=torch.full((R,), -1, dtype=torch.int32, device=self.device))
+            if n_samp:
+                step = hip.dec_sample_step
+                rules.update(temperature=temperature, seed=sample_call_seed(seed))
+                if n_samp > 1:
+                    logits = logits.repeat_interleave(n_samp, dim=0)
             select = lambda logits, i, last: step(logits, V, finished=finished, n_unfinished=n_unf, tokens=tokens, logprobs=logprobs, t=i,
                                                   eos_id=eos, pad_id=pad, suppress=sup, begin_suppress=bsup, first=i == 0, embed_tokens=E,
                                                   embed_positions=Pz, next_pos=P + i, h_next=None if last else h_next, **rules)
@@ -897,14 +940,25 @@ class WhisperSeq2Seq:
             if no_speech is not None:
                 no_speech = np.exp(no_speech.double().cpu().numpy())
         lens = np.array([int(np.argmax(r == eos)) + 1 if (r == eos).any() else steps for r in tok], dtype=np.int64)
+        samples = sample_lps = sums = None
+        if n_samp:  # the candidates of an utterance in row order; the ranking's choice fills the other fields
+            sums = lp.sum(-1)  # (a finished row's log-probs are 0 already)
+            samples, sample_lps, pick = [], [], []
+            for b in range(B):
+                rows = range(b * n_samp, (b + 1) * n_samp)
+                cands = [(tok[r, :lens[r]].tolist(), float(sums[r]), bool((tok[r] == eos).any()), r) for r in rows]
+                samples.append([(c[0], c[1]) for c in cands])
+                sample_lps.append([lp[r, :lens[r]].copy() for r in rows])
+                pick.append(rows[beam_rank(cands, length_penalty)])
+            tok, lp, lens, sums = tok[pick], lp[pick], lens[pick], sums[pick]
         n = int(lens.max())
         tok, lp = tok[:, :n].copy(), lp[:, :n].copy()
         for b in range(B):  # (a finished row emits pad with log-probability 0 already; this also covers pad == eos)
             tok[b, lens[b]:] = pad
             lp[b, lens[b]:] = 0.0
-        s = lp.sum(-1)
+        s = lp.sum(-1) if sums is None else sums  # (sampling: the chosen candidates' sums as ``samples`` lists them)
         return GenerateResult(tokens=[tok[b, :lens[b]].tolist() for b in range(B)], lens=lens, token_array=tok, logprobs=lp, sum_logprob=s,
-                              avg_logprob=s / (lens + 1), steps=steps, no_speech_prob=no_speech)
+                              avg_logprob=s / (lens + 1), steps=steps, no_speech_prob=no_speech, samples=samples, sample_logprobs=sample_lps)
 
     def transcribe(self, waveforms, language=None, task: str = "transcribe", no_speech_threshold: Optional[float] = 0.6,
                    logprob_threshold: Optional[float] = -1.0, batch_size: int = 8, **kw):
