@@ -14,7 +14,7 @@ EXTRA ?=
 # (The library reads nothing from the environment.  The development switches of earlier rounds and their `make DEV=1` build were
 # retired after commit 1fc4c62, the last to have them; the A/B numbers in DESIGN.md and profiles/ that name a switch were taken
 # with them.  A variant is now an EXTRA= build, as above.)
-HIPFLAGS := $(EXTRA) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-lambda-capture -Iinclude -ffp-contract=fast -mllvm -amdgpu-mfma-vgpr-form -mllvm -amdgpu-atomic-optimizer-strategy=None
+HIPFLAGS := $(EXTRA) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-lambda-capture -Iinclude -ffp-contract=fast -mllvm -amdgpu-mfma-vgpr-form -mllvm -amdgpu-atomic-optimizer-strategy=None
 SRCS := $(wildcard $(CSRC)/*.hip) $(wildcard $(CSRC)/*.cpp)
 OBJS := $(patsubst $(CSRC)/%,$(OBJ)/%.o,$(SRCS))
 

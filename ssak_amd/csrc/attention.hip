@@ -113,52 +113,34 @@ __device__ __forceinline__ void fill_colmul(uint32_t* cmt, int n) {
   for (int k = threadIdx.x; k < n; k += 256) cmt[k] = drop_colmul((uint32_t)k);
 }
 
-// LDS tile images (64 rows x 128 B each):
-//   row-read image  : chunk c of row r at c ^ ((r >> 1) & 7)      -> ds_read_b128 fragments (row on the lane)
-//   transpose image : chunk c of row r at c ^ (r & 6)             -> ds_read_b64_tr_b16 fragments (column on the lane)
-//   dual image      : = the transpose image.  `ds_read_b128` is served in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19,
-//                     28-31}, ... (MI355X_MICROARCH.md, LDS), not in runs of eight lanes, and under THOSE groups the transpose
-//                     image is conflict-free for row reads as well (enumerated on the host: 0 extra cycles for both kinds of
-//                     fragment; the rotated swizzle c ^ rotl3((r >> 1) & 7) this image used through round 2 was designed for
-//                     contiguous groups and was two-way conflicted on every row read: SQ_LDS_BANK_CONFLICT = 26 % / 40 % of
-//                     the LDS cycles of the dK-dV / dQ kernels, profiles/r03_pmc_sq.json).  One image per tensor instead of
-//                     two: a wave issues an LDS-DMA instruction only every ~110 cycles, and the backward kernels staged 6 (dQ)
-//                     and 8 (dK / dV) per wave and tile.
-#ifdef ATT_OLD_DUAL  // A/B: the rotated swizzle of rounds 1-2
-__device__ __forceinline__ int dual_swz(int r) {
-  const int x = (r >> 1) & 7;
-  return ((x << 1) & 7) | (x >> 2);
-}
-#else
-__device__ __forceinline__ int dual_swz(int r) { return r & 6; }
-#endif
-__device__ __forceinline__ void dma_tile(__amdgpu_buffer_rsrc_t rsrc, char* lds_tile, uint32_t col_byte, long ld_bytes,
-                                         int row0, int nrows_total, int image /* 0 row-read, 1 transpose, 2 dual */, int wave, int lane) {
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int S = (wave * 2 + j) * 64 + lane;
-    const int r = S >> 3, pc = S & 7;
-    const int c = image == 2 ? (pc ^ dual_swz(r)) : image == 1 ? (pc ^ (r & 6)) : (pc ^ ((r >> 1) & 7));
-    const int gr = row0 + r;
-    const uint32_t off = gr < nrows_total ? (uint32_t)((long)gr * ld_bytes + col_byte + c * 16) : 0x80000000u;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(lds_tile + (wave * 2 + j) * 1024), 16, off, 0, 0, 0);
-  }
-}
+// LDS tile images (64 rows x 128 B each), chosen by the swizzle the LDS-DMA applies on the source side:
+//   row-read image  : chunk c of row r at c ^ ((r >> 1) & 7)      -> ds_read_b128 fragments (row on the lane): frag_rows
+//   transpose image : chunk c of row r at c ^ (r & 6)             -> ds_read_b64_tr_b16 fragments (column on the lane):
+//                     frag_cols_perm -- AND ds_read_b128 row fragments: frag_rows_tr
+// The transpose image is conflict-free for row reads too.  `ds_read_b128` is served in the lane groups {0-3, 12-15, 20-27},
+// {4-11, 16-19, 28-31}, ... (MI355X_MICROARCH.md, LDS), not in runs of eight lanes, and under THOSE groups c ^ (r & 6) costs 0
+// extra cycles for both kinds of fragment (enumerated on the host).  So a tensor that is read both ways -- K in the dQ kernel, Q
+// and dO in the dK / dV kernel -- is staged once, as a transpose image: a wave issues an LDS-DMA instruction only every ~110
+// cycles, and with one image per kind of read the backward kernels staged 6 (dQ) and 8 (dK / dV) per wave and tile.  (Through
+// round 2 such tensors had a third image, c ^ rotl3((r >> 1) & 7), designed for contiguous lane groups; it was two-way
+// conflicted on every row read: SQ_LDS_BANK_CONFLICT = 26 % / 40 % of the LDS cycles of the dK-dV / dQ kernels,
+// profiles/r03_pmc_sq.json.)  The forward reads K by rows only and V by columns only and uses one image of each kind.
+enum class TileImage { RowRead, Transpose };
 
-// The same staging with the per-lane offsets computed ONCE and the tile's first row carried by the buffer descriptor: per tile the
-// address work is scalar (base += row0 rows, records -= the same) -- dma_tile() spends an add, a compare and a select per instruction
-// and tile on the VALU (12 per key tile in the forward / dQ kernels, 12 in dK / dV), in kernels whose time IS their VALU count.  Rows
-// beyond the tensor fall outside the shrunken descriptor and come back as zeros, as before.
+// Staging: the per-lane offsets are computed ONCE and the tile's first row is carried by the buffer descriptor, so per tile the
+// address work is scalar (base += row0 rows, records -= the same).  Offsets per tile cost an add, a compare and a select per
+// instruction on the VALU (12 per key tile in the forward / dQ kernels, 12 in dK / dV), in kernels whose time IS their VALU count.
+// Rows beyond the tensor fall outside the shrunken descriptor and come back as zeros.
 struct DmaOff {
   uint32_t o[2];
 };
-__device__ __forceinline__ DmaOff dma_offsets(uint32_t col_byte, long ld_bytes, int image, int wave, int lane) {
+__device__ __forceinline__ DmaOff dma_offsets(uint32_t col_byte, long ld_bytes, TileImage image, int wave, int lane) {
   DmaOff d;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int S = (wave * 2 + j) * 64 + lane;
     const int r = S >> 3, pc = S & 7;
-    const int c = image == 2 ? (pc ^ dual_swz(r)) : image == 1 ? (pc ^ (r & 6)) : (pc ^ ((r >> 1) & 7));
+    const int c = image == TileImage::Transpose ? (pc ^ (r & 6)) : (pc ^ ((r >> 1) & 7));
     d.o[j] = (uint32_t)((long)r * ld_bytes + col_byte + c * 16);
   }
   return d;
@@ -180,6 +162,12 @@ __device__ __forceinline__ bf16x8 frag_rows(const char* tile, int sub, int kk, i
   const int c = kk * 4 + (lane >> 4);
   return *reinterpret_cast<const bf16x8*>(tile + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
 }
+// the same fragment read from a TRANSPOSE image
+__device__ __forceinline__ bf16x8 frag_rows_tr(const char* tile, int sub, int kk, int lane) {
+  const int r = 16 * sub + (lane & 15);
+  const int c = kk * 4 + (lane >> 4);
+  return *reinterpret_cast<const bf16x8*>(tile + r * 128 + ((c ^ (r & 6)) << 4));
+}
 // transpose fragment from the transpose image: A[row = column 16*ci + (lane&15) of the tile][k = tile rows]:
 //   element j < 4: tile row rbase + 4*(lane>>4) + j, j >= 4: tile row rbase + 16 + 4*(lane>>4) + (j-4)
 // (this is the k permutation of an accumulator tile used as the other operand)
@@ -187,24 +175,7 @@ __device__ __forceinline__ bf16x8 frag_cols_perm(const char* tile, int ci, int r
   const int g = lane >> 4, q4 = (lane >> 2) & 3, p4 = lane & 3;
   const int r = rbase + 4 * g + q4;
   const int ch = 2 * ci + (p4 >> 1);
-  const char* a = tile + r * 128 + ((ch ^ (r & 6)) << 4) + (p4 & 1) * 8;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(a));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(a + 16 * 128));
-  s16x8_t v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// the same two fragments from a dual image
-__device__ __forceinline__ bf16x8 frag_rows_d(const char* tile, int sub, int kk, int lane) {
-  const int r = 16 * sub + (lane & 15);
-  const int c = kk * 4 + (lane >> 4);
-  return *reinterpret_cast<const bf16x8*>(tile + r * 128 + ((c ^ dual_swz(r)) << 4));
-}
-__device__ __forceinline__ bf16x8 frag_cols_perm_d(const char* tile, int ci, int rbase, int lane) {
-  const int g = lane >> 4, q4 = (lane >> 2) & 3, p4 = lane & 3;
-  const int r = rbase + 4 * g + q4;
-  const int ch = 2 * ci + (p4 >> 1);
-  const char* a = tile + r * 128 + ((ch ^ dual_swz(r)) << 4) + (p4 & 1) * 8;  // row + 16: the same swizzle
+  const char* a = tile + r * 128 + ((ch ^ (r & 6)) << 4) + (p4 & 1) * 8;  // row + 16: the same swizzle
   const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(a));
   const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(a + 16 * 128));
   s16x8_t v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
@@ -339,7 +310,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnParams p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) oacc[qs][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  const DmaOff koff = dma_offsets(kcol, ld * 2, 0, wave, lane), voff = dma_offsets(vcol, ld * 2, 1, wave, lane);
+  const DmaOff koff = dma_offsets(kcol, ld * 2, TileImage::RowRead, wave, lane), voff = dma_offsets(vcol, ld * 2, TileImage::Transpose, wave, lane);
   if (nkt > 0) {
     dma_tile_at(rsrc, smem, koff, wave);
     dma_tile_at(rsrc, smem + TILE_BYTES, voff, wave);
@@ -465,26 +436,11 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnParams p) {
 }
 
 // ================================================================================================ backward
-// delta[b,h,q] = sum_d dO[q,d] * O[q,d]   (one wave per row of [B*F, H], 64 lanes = 64 d of one head at a time)
-__global__ __launch_bounds__(256) void attn_delta_kernel(const bf16* __restrict__ dctx, const bf16* __restrict__ ctx,
-                                                         float* __restrict__ delta, int B, int F, int nh, int H) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (long)B * F) return;
-  const int b = (int)(row / F), q = (int)(row % F);
-  for (int h = 0; h < nh; ++h) {
-    const long o = row * H + h * HD + lane;
-    float v = (float)dctx[o] * (float)ctx[o];
-    v = wave_sum(v);
-    if (lane == 0) delta[((long)b * nh + h) * F + q] = v;
-  }
-}
-
 // dQ: workgroup = 128 queries of one (b, h); sweeps the keys.  Same orientation as the forward:
 //   S^T[key][q], dP^T[key][q] = V dO^T, dS^T = P^T * (dP^T * mask/(1-p) - delta[q]); dQ^T[d][q] += K^T[d][key] dS^T[key][q].
 template <bool DROP, int NQS>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 stages x (K dual image | V rows)
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 stages x (K | V), both transpose images
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const AttnBlock ab = attn_block();
   const int b = ab.b, h = ab.h, q0 = ab.blk * (64 * NQS);
@@ -533,7 +489,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnParams p)
     for (int i = 0; i < 4; ++i) dq[qs][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const uint32_t* cmt = reinterpret_cast<const uint32_t*>(smem + 2 * 2 * TILE_BYTES);  // [nkt * 64] key multipliers (DROP)
   if (DROP) fill_colmul(reinterpret_cast<uint32_t*>(smem + 2 * 2 * TILE_BYTES), nkt * KT);
-  const DmaOff koff = dma_offsets(kcol, ld * 2, 2, wave, lane), voff = dma_offsets(vcol, ld * 2, 2, wave, lane);
+  const DmaOff koff = dma_offsets(kcol, ld * 2, TileImage::Transpose, wave, lane), voff = dma_offsets(vcol, ld * 2, TileImage::Transpose, wave, lane);
   auto issue = [&](int kt, int stage) {
     char* s0 = smem + stage * 2 * TILE_BYTES;
     const __amdgpu_buffer_rsrc_t rn = rsrc_rows(base, ld * 2, kt * KT, F);
@@ -546,7 +502,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnParams p)
     __builtin_amdgcn_s_waitcnt(0x0f70);
     __syncthreads();
     if (kt + 1 < nkt) issue(kt + 1, cur ^ 1);
-    const char* k_rows = smem + cur * 2 * TILE_BYTES;  // one dual image of K serves the row and the transposing reads
+    const char* k_rows = smem + cur * 2 * TILE_BYTES;  // one transpose image of K serves the row and the transposing reads
     const char* k_tr = k_rows;
     const char* v_rows = k_rows + TILE_BYTES;
     const int k0 = kt * KT;
@@ -559,8 +515,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnParams p)
 #pragma unroll
         for (int kh = 0; kh < 2; ++kh) {
           const int ks = 2 * t2 + kh;
-          const bf16x8 ka = frag_rows_d(k_rows, ks, 0, lane), kb = frag_rows_d(k_rows, ks, 1, lane);
-          const bf16x8 va = frag_rows_d(v_rows, ks, 0, lane), vb = frag_rows_d(v_rows, ks, 1, lane);
+          const bf16x8 ka = frag_rows_tr(k_rows, ks, 0, lane), kb = frag_rows_tr(k_rows, ks, 1, lane);
+          const bf16x8 va = frag_rows_tr(v_rows, ks, 0, lane), vb = frag_rows_tr(v_rows, ks, 1, lane);
 #pragma unroll
           for (int qs = 0; qs < NQS; ++qs) {
             f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = {0.f, 0.f, 0.f, 0.f};
@@ -614,7 +570,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnParams p)
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const bf16x8 ka = frag_cols_perm_d(k_tr, i, 32 * t2, lane);
+        const bf16x8 ka = frag_cols_perm(k_tr, i, 32 * t2, lane);
 #pragma unroll
         for (int qs = 0; qs < NQS; ++qs) dq[qs][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, dsb[qs], dq[qs][i], 0, 0, 0);
       }
@@ -655,7 +611,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnParams p)
 // a copy of a per-lane vector (4 v_mov per S tile, 32 per query tile and lane: a tenth of the loop's VALU).
 template <bool DROP, int NKS, bool MASK>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 stages x (Q dual image | dO dual image), then lse|delta|seed per stage
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 stages x (Q | dO), both transpose images, then lse|delta|seed per stage
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const AttnBlock ab = attn_block();
   const int b = ab.b, h = ab.h, key0 = ab.blk * (64 * NKS);
@@ -702,7 +658,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnParams p
       dk[ks][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
       dv[ks][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-  const DmaOff qoff = dma_offsets(qcol, ld * 2, 2, wave, lane), dooff = dma_offsets(qcol, (long)H * 2, 2, wave, lane);
+  const DmaOff qoff = dma_offsets(qcol, ld * 2, TileImage::Transpose, wave, lane), dooff = dma_offsets(qcol, (long)H * 2, TileImage::Transpose, wave, lane);
   const bf16* const do_base = p.dctx + (long)b * F * H;
   auto issue = [&](int qt, int stage) {
     char* s0 = smem + stage * 2 * TILE_BYTES;
@@ -746,7 +702,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnParams p
       if (qt + 2 < nqt) load_stat(qt + 2);  // ... and the next ones, ahead of the DMA in the memory queue
       issue(qt + 1, cur ^ 1);
     }
-    const char* q_rows = smem + cur * 2 * TILE_BYTES;  // dual images: row reads and transposing reads from the same tile
+    const char* q_rows = smem + cur * 2 * TILE_BYTES;  // transpose images: row reads and transposing reads from the same tile
     const char* q_tr = q_rows;
     const char* do_rows = q_rows + TILE_BYTES;
     const char* do_tr = do_rows;
@@ -761,8 +717,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnParams p
 #pragma unroll
         for (int qh = 0; qh < 2; ++qh) {
           const int qsb = 2 * t2 + qh;
-          const bf16x8 qa = frag_rows_d(q_rows, qsb, 0, lane), qb = frag_rows_d(q_rows, qsb, 1, lane);
-          const bf16x8 da = frag_rows_d(do_rows, qsb, 0, lane), db = frag_rows_d(do_rows, qsb, 1, lane);
+          const bf16x8 qa = frag_rows_tr(q_rows, qsb, 0, lane), qb = frag_rows_tr(q_rows, qsb, 1, lane);
+          const bf16x8 da = frag_rows_tr(do_rows, qsb, 0, lane), db = frag_rows_tr(do_rows, qsb, 1, lane);
 #pragma unroll
           for (int ks = 0; ks < NKS; ++ks) {
             // keys beyond the key length (a per-lane constant) start S at -3e38: exp2(-huge) = 0, no select per element
@@ -813,8 +769,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnParams p
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const bf16x8 doa = frag_cols_perm_d(do_tr, i, 32 * t2, lane);
-        const bf16x8 qa = frag_cols_perm_d(q_tr, i, 32 * t2, lane);
+        const bf16x8 doa = frag_cols_perm(do_tr, i, 32 * t2, lane);
+        const bf16x8 qa = frag_cols_perm(q_tr, i, 32 * t2, lane);
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
           dv[ks][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(doa, pdb[ks], dv[ks][i], 0, 0, 0);

@@ -1,15 +1,22 @@
-// Feature-encoder front end and positional-convolution weight plumbing.  gfx950.
+// Feature-encoder front end: the first convolution of the wav2vec 2.0 feature encoder, forward and backward.  gfx950.
 //
-//  * conv0 (C_in = 1, k = 10, s = 5) + GroupNorm(C groups = per-channel over time) + GELU, written
-//    channels-last in bf16 (transformers modeling_wav2vec2.py:302-323).  The fp32 pre-norm activation
-//    (65 MB / utterance at 10 s) is never materialised: pass 1 recomputes the 10-tap dot product to get the
-//    per-channel statistics (fp64 atomics), pass 2 recomputes it again, normalises, applies GELU and writes
-//    bf16 once.  HBM-bound on the 32.7 MB / utterance bf16 store.
-//  * Conv1d weight re-layout [Co, Ci, k] -> [Co, k, Ci] bf16: with channels-last activations a strided
-//    Conv1d is then a GEMM whose A rows overlap (lda = stride * Ci), no im2col.
-//  * Positional conv (:326-368): weight_norm(dim=2) materialisation w = g v / ||v|| into the forward GEMM
-//    layout [H][K][H/G] and the flipped/transposed layout of the input-gradient GEMM, its backward to
-//    (g, v), and the zero-padded per-group activation packing that turns the grouped conv into batched GEMMs.
+//  * conv0 (C_in = 1, k = 10, s = 5) + GroupNorm(C groups = per-channel over time) + GELU, written channels-last
+//    (transformers modeling_wav2vec2.py:302-323).  The fp32 pre-norm activation (65 MB / utterance at 10 s) is never
+//    materialised, and the GroupNorm statistics need no pass over it either:
+//      - statistics: conv0 is linear, so sum_t y and sum_t y^2 per channel follow in closed form from 67 moments of the INPUT
+//        per utterance (conv0_moments_kernel: fp64 per-workgroup partials, fixed summation order; conv0_channel_stats_kernel:
+//        (mean, rstd) per (utterance, channel)).  The feature extractor's zero-mean / unit-variance normalisation folds into
+//        the same moments for raw waveforms.
+//      - apply: conv0_mfma_kernel (bf16 out, C = 512) evaluates the ten-tap dot product on the matrix cores from a hi / lo
+//        bf16 split and runs affine + GELU on the VALU; conv0_kernel is the VALU fallback for every other channel count and
+//        for fp32 output (the fp32-exact verification mode).
+//  * conv0 + bias only (conv0_bias_kernel) for the layer-norm feature encoder (XLS-R), which normalises per frame afterwards.
+//  * Conv1d weight re-layout [Co, Ci, k] -> [Co, k, Ci]: with channels-last activations a strided Conv1d is then a GEMM whose
+//    A rows overlap (lda = stride * Ci), no im2col.
+//  * The kernels that run only when the feature encoder trains (--no_freeze): col2im for the input gradient of the strided
+//    convolutions, the conv0 + GroupNorm + GELU backward (two recomputing passes, conv0_bwd_kernel, and their fixed-order
+//    sums), the conv0 weight gradient of the layer-norm encoder (conv0_wgrad_kernel) and the per-utterance slab sum.
+// (The positional convolution and its weight plumbing: posconv.hip.)
 #include <cstdlib>
 
 #include "kernels.h"
@@ -17,18 +24,16 @@
 namespace {
 
 constexpr int KS0 = 10, ST0 = 5;  // conv0 taps / stride
-constexpr int FR_STATS = 1024, FR_APPLY = 128;  // frames per workgroup (statistics pass: few, contended fp64 atomics)
+constexpr int FR_STATS = 1024, FR_APPLY = 128;  // frames per workgroup (moments / backward passes: few, long; apply: many)
 
-// (Only the APPLY form is instantiated.  The other form left per-workgroup (sum y, sum y^2) partials of the convolution's output
-// for GroupNorm; the statistics now come from the input's moments in closed form: conv0_moments_kernel below.)
-template <typename OT, bool APPLY, int FR0>
+// conv0 + GroupNorm + GELU apply pass on the VALU: thread = (channel quad, frame lane); `sums` = (mean, rstd) per (utterance,
+// channel) from conv0_channel_stats_kernel
+template <typename OT, int FR0>
 __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                    OT* __restrict__ out, double* __restrict__ stats,
-                                                    const double* __restrict__ sums, int T, int T0, int C) {
+                                                    OT* __restrict__ out, const double* __restrict__ sums, int T, int T0, int C) {
   constexpr int NS0 = (FR0 - 1) * ST0 + KS0;
   __shared__ float xs[NS0];
-  __shared__ float red[256][9];
   const int b = blockIdx.y;
   const int f0 = blockIdx.x * FR0;
   const int nq = C >> 2;        // channel quads
@@ -46,17 +51,14 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ x,
 #pragma unroll
     for (int k = 0; k < KS0; ++k) wr[j][k] = w[(q * 4 + j) * KS0 + k];
   float mu[4], rs[4], ga[4], be[4];
-  if (APPLY) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      mu[j] = (float)sums[((size_t)b * C + q * 4 + j) * 2];  // (mean, 1 / sqrt(var + eps)) per (utterance, channel)
-      rs[j] = (float)sums[((size_t)b * C + q * 4 + j) * 2 + 1];
-      ga[j] = gamma[q * 4 + j];
-      be[j] = beta[q * 4 + j];
-    }
+  for (int j = 0; j < 4; ++j) {
+    mu[j] = (float)sums[((size_t)b * C + q * 4 + j) * 2];  // (mean, 1 / sqrt(var + eps)) per (utterance, channel)
+    rs[j] = (float)sums[((size_t)b * C + q * 4 + j) * 2 + 1];
+    ga[j] = gamma[q * 4 + j];
+    be[j] = beta[q * 4 + j];
   }
   __syncthreads();
-  float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
   for (int f = fli; f < nfr; f += fl) {
     float xv[KS0];
 #pragma unroll
@@ -69,40 +71,10 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ x,
       for (int k = 0; k < KS0; ++k) a = fmaf(wr[j][k], xv[k], a);
       v[j] = a;
     }
-    if (APPLY) {
-      float o[4];
+    float o[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = gelu_s<OT>((v[j] - mu[j]) * rs[j] * ga[j] + be[j]);
-      st4<OT>(out + ((size_t)b * T0 + f0 + f) * C + q * 4, f_to_chunk4<OT>(o));
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s1[j] += v[j];
-        s2[j] = fmaf(v[j], v[j], s2[j]);
-      }
-    }
-  }
-  if (!APPLY) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      red[threadIdx.x][j] = s1[j];
-      red[threadIdx.x][4 + j] = s2[j];
-    }
-    __syncthreads();
-    if (fli == 0) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        double a = 0.0, c = 0.0;
-        for (int l = 0; l < fl; ++l) {
-          a += red[l * nq + q][j];
-          c += red[l * nq + q][4 + j];
-        }
-        // per-workgroup partial, for a second pass that sums them in a fixed order
-        double* dst = stats + (((size_t)b * gridDim.x + blockIdx.x) * C + q * 4 + j) * 2;
-        dst[0] = a;
-        dst[1] = c;
-      }
-    }
+    for (int j = 0; j < 4; ++j) o[j] = gelu_s<OT>((v[j] - mu[j]) * rs[j] * ga[j] + be[j]);
+    st4<OT>(out + ((size_t)b * T0 + f0 + f) * C + q * 4, f_to_chunk4<OT>(o));
   }
 }
 
@@ -157,13 +129,8 @@ __global__ __launch_bounds__(256) void conv0_bias_kernel(const float* __restrict
 //   in LDS (64 B per frame), the weight fragments once per wave in registers.  Orientation out^T[channel][frame] = W X^T: a
 //   lane then holds four consecutive channels of one frame, which go through a wave-private, XOR-swizzled LDS tile
 //   ([16 frames][128 channels], 8-byte writes) and leave as 16-byte stores of whole 256-byte row segments.
-#ifndef C0M_HALF_SWAP
-#define C0M_HALF_SWAP 1  // (0: the round-2 store tile, for A/B builds)
-#endif
 constexpr int C0M_FR = 128;
-#ifndef C0M_SUB
-#define C0M_SUB 4  // blocks of C0M_FR frames per workgroup
-#endif
+constexpr int C0M_SUB = 4;  // blocks of C0M_FR frames per workgroup
 constexpr int C0M_NS = (C0M_FR - 1) * ST0 + KS0;  // 645 input samples
 typedef __attribute__((ext_vector_type(2))) float c0_f32x2;
 
@@ -297,7 +264,7 @@ __global__ __launch_bounds__(256) void conv0_mfma_kernel(const float* __restrict
         // lanes of a store group (one g, lc = 0..15) write 8 bytes each = all 32 banks exactly when their 8-byte slots differ:
         // the chunk swizzle alone sends rows lc and lc + 8 to the same slot (2-way conflict on every store: rocprofv3 counted
         // SQ_LDS_BANK_CONFLICT = 24 % of the LDS cycles), so rows 8..15 also swap the two halves of a chunk (undone at the read)
-        *reinterpret_cast<bf16x4*>(ost + lc * 256 + (((2 * ct + (g >> 1)) ^ lc) << 4) + (((g & 1) ^ (C0M_HALF_SWAP ? lc >> 3 : 0)) << 3)) = o;
+        *reinterpret_cast<bf16x4*>(ost + lc * 256 + (((2 * ct + (g >> 1)) ^ lc) << 4) + (((g & 1) ^ (lc >> 3)) << 3)) = o;
       }
     }
     // the tile leaves as whole 256-byte row segments: lane = (row 4 pass + g, chunk lc)
@@ -305,7 +272,7 @@ __global__ __launch_bounds__(256) void conv0_mfma_kernel(const float* __restrict
     for (int pass = 0; pass < 4; ++pass) {
       const int r = 4 * pass + g;
       f32x4 v = *reinterpret_cast<const f32x4*>(ost + r * 256 + ((lc ^ r) << 4));
-      if (C0M_HALF_SWAP && pass >= 2) v = (f32x4){v[2], v[3], v[0], v[1]};  // rows 8..15 were stored with their chunk halves swapped
+      if (pass >= 2) v = (f32x4){v[2], v[3], v[0], v[1]};  // rows 8..15 were stored with their chunk halves swapped
       const int frame = f0 + 16 * ft + r;
       if (frame < T0) *reinterpret_cast<f32x4*>(out + ((size_t)b * T0 + frame) * C + 128 * wave + 8 * lc) = v;
     }
@@ -600,134 +567,6 @@ __global__ void conv_w_rearrange_kernel(const float* __restrict__ w, OT* __restr
   }
 }
 
-// Per-tap sums over the [H][cg] rows of v[o][c][k] (k fastest): ||v_k||^2, or the dot product with the weight gradient
-// dwf[group][k][c][n] (o = group * cg + n).  One workgroup per (group, c) pair, a thread per tap k: the reads of v are
-// coalesced over k, each thread walks the cg contiguous n of its dwf row; partial[(group * cg + c)][k], then a fixed-order
-// reduction.  (The first version used 256 two-wave workgroups striding over all rows with an uncoalesced dwf gather and a
-// single-workgroup serial finalize: 89 + 60 us for 19 MB.)
-__global__ void posconv_colnorm_kernel(const float* __restrict__ v, const float* __restrict__ dwf, int G, int K, int cg,
-                                       float* __restrict__ partial) {
-  const int k = threadIdx.x;
-  if (k >= K) return;
-  const int g = blockIdx.x / cg, c = blockIdx.x % cg;
-  float s = 0.f;
-  const float* vp = v + ((long)(g * cg) * cg + c) * K + k;  // + n * cg * K
-  if (dwf) {
-    const float* dp = dwf + (((long)g * K + k) * cg + c) * cg;  // + n
-    // (unrolled: the loads of eight rows in flight per thread; one at a time this kernel ran at HBM latency, 34 us for 19 MB)
-#pragma unroll 8
-    for (int n = 0; n < cg; ++n) s = fmaf(vp[(long)n * cg * K], dp[n], s);
-  } else {
-#pragma unroll 8
-    for (int n = 0; n < cg; ++n) {
-      const float a = vp[(long)n * cg * K];
-      s = fmaf(a, a, s);
-    }
-  }
-  partial[(size_t)blockIdx.x * K + k] = s;
-}
-// out[k] = sum over nblk partial rows, fixed order; workgroup = 64 taps x 16 row groups
-__global__ __launch_bounds__(1024) void posconv_colnorm_finalize_kernel(const float* __restrict__ partial, int nblk, int K, float* __restrict__ out) {
-  __shared__ float red[16][65];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int k = blockIdx.x * 64 + cx;
-  float s = 0.f;
-  if (k < K) {
-#pragma unroll 8
-    for (int b = ry; b < nblk; b += 16) s += partial[(size_t)b * K + k];  // (eight loads in flight: two workgroups do all of it)
-  }
-  red[ry][cx] = s;
-  __syncthreads();
-  if (ry == 0 && k < K) {
-    float t = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t += red[r][cx];
-    out[k] = t;
-  }
-}
-
-// w = g[k] v / ||v_k|| in the two bf16 layouts the GEMMs read: wf[o][k][c] (forward / dX operand) and
-// wb[group][c][K-1-k][n] (o = group * cg + n).  Both are (c, k) <-> (k, c|n) transposes of v[o][c][k]: a workgroup stages
-// one [cg][K] slab through LDS -- slab o for wf (blocks [0, H)), the slab of (group, c) over its cg output channels for wb
-// (blocks [H, 2H)) -- so that global reads and writes are both contiguous (the element-wise version scattered 2-byte
-// stores: 48 us for 38 MB).
-template <typename OT>
-__global__ __launch_bounds__(256) void posconv_materialize_kernel(const float* __restrict__ g, const float* __restrict__ v,
-                                                                  const float* __restrict__ nsq, OT* __restrict__ wf,
-                                                                  OT* __restrict__ wb, int H, int cg, int K) {
-  extern __shared__ float slab[];  // [cg][K + 1]
-  const int KP = K + 1;
-  const bool back = (int)blockIdx.x >= H;
-  const int id = back ? blockIdx.x - H : blockIdx.x;
-  if (!back) {
-    const float* src = v + (long)id * cg * K;  // v[o = id][c][k]
-    for (int j = threadIdx.x; j < cg * K; j += 256) {
-      const int c = j / K, k = j % K;
-      slab[c * KP + k] = g[k] * src[j] * rsqrtf(nsq[k]);
-    }
-    __syncthreads();
-    OT* dst = wf + (long)id * K * cg;  // wf[o][k][c]
-    for (int j = threadIdx.x; j < K * cg; j += 256) dst[j] = (OT)slab[(j % cg) * KP + j / cg];
-  } else {
-    const int grp = id / cg, c = id % cg;
-    for (int j = threadIdx.x; j < cg * K; j += 256) {
-      const int nn = j / K, k = j % K;
-      slab[nn * KP + k] = g[k] * v[(((long)grp * cg + nn) * cg + c) * K + k] * rsqrtf(nsq[k]);
-    }
-    __syncthreads();
-    OT* dst = wb + (long)id * K * cg;  // wb[group][c][kk][n], kk = K - 1 - k
-    for (int j = threadIdx.x; j < K * cg; j += 256) dst[j] = (OT)slab[(j % cg) * KP + (K - 1 - j / cg)];
-  }
-}
-
-// weight-norm backward: dv[o][c][k] += g[k] / ||v_k|| (d - v dot[k] / ||v_k||^2), dg[k] += dot[k] / ||v_k||, with
-// d = dwf[group][k][c][n].  One workgroup per (group, c): the dwf rows (contiguous over n) go through LDS and leave
-// as rows contiguous over k.
-__global__ __launch_bounds__(256) void posconv_wbwd_kernel(const float* __restrict__ dwf, const float* __restrict__ g,
-                                                           const float* __restrict__ v, const float* __restrict__ nsq,
-                                                           const float* __restrict__ dot, float* __restrict__ dg,
-                                                           float* __restrict__ dv, int H, int cg, int K) {
-  extern __shared__ float slab[];  // [K][cg + 1]
-  const int CP = cg + 1;
-  const int grp = blockIdx.x / cg, c = blockIdx.x % cg;
-  for (int j = threadIdx.x; j < K * cg; j += 256) {
-    const int k = j / cg, nn = j % cg;
-    slab[k * CP + nn] = dwf[(((long)grp * K + k) * cg + c) * cg + nn];
-  }
-  __syncthreads();
-  for (int j = threadIdx.x; j < cg * K; j += 256) {
-    const int nn = j / K, k = j % K;
-    const long e = (((long)grp * cg + nn) * cg + c) * K + k;
-    const float inv = rsqrtf(nsq[k]);
-    dv[e] += g[k] * inv * (slab[k * CP + nn] - v[e] * dot[k] * inv * inv);
-  }
-  if (blockIdx.x == 0)
-    for (int k = threadIdx.x; k < K; k += 256) dg[k] += dot[k] * rsqrtf(nsq[k]);
-}
-
-template <typename T>
-__global__ void posconv_pack_kernel(const T* __restrict__ h, T* __restrict__ pg, int B, int F, int H, int G,
-                                    int lead, int RS, long rows_total) {
-  const int cg = H / G, cpr = cg >> 3;
-  const long n = rows_total * G * cpr;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-    const int cc = (int)(e % cpr);
-    const long r = (e / cpr) % rows_total;
-    const int g = (int)(e / ((long)cpr * rows_total));
-    const long rr = r - lead;
-    Chunk8<T> val = {};
-    if (rr >= 0) {
-      const int b = (int)(rr / RS), t = (int)(rr % RS);
-      if (b < B && t < F) val = ld8<T>(h + ((long)b * F + t) * H + g * cg + cc * 8);
-    }
-    st8<T>(pg + ((long)g * rows_total + r) * cg + cc * 8, val);
-  }
-}
-
-}  // namespace
-
-namespace {
-
 // conv0 weight gradient for the layer-norm feature encoder (the gradient w.r.t. the conv output is materialised there):
 // dw[c][k] = sum_{b,t} d[b,t,c] * x[b, stride t + k].  Workgroup = a contiguous range of frames of one utterance; thread =
 // two channels, 2 * ksize accumulators in registers; the frame's taps are read once per workgroup into LDS.
@@ -829,7 +668,7 @@ int k_conv0_gn_gelu_t(const float* x, const float* w, const float* gamma, const 
       return SSAK_OK;
     }
   }
-  conv0_kernel<OT, true, FR_APPLY><<<dim3(ssak_cdiv(T0, FR_APPLY), B), 256, 0, st>>>(x, w, gamma, beta, out, nullptr, sums, T, T0, C);
+  conv0_kernel<OT, FR_APPLY><<<dim3(ssak_cdiv(T0, FR_APPLY), B), 256, 0, st>>>(x, w, gamma, beta, out, sums, T, T0, C);
   SSAK_LAUNCH_CHECK();
   return SSAK_OK;
 }
@@ -848,52 +687,6 @@ int k_conv0_bias_t(const float* x, const float* w, const float* bias, OT* out, i
 template <typename OT>
 int k_conv_weight_rearrange_t(const float* w, OT* out, int Co, int Ci, int k, hipStream_t st) {
   conv_w_rearrange_kernel<OT><<<min(2048, ssak_cdiv((long)Co * Ci * k, 256)), 256, 0, st>>>(w, out, Co, Ci, k);
-  SSAK_LAUNCH_CHECK();
-  return SSAK_OK;
-}
-
-template <typename OT>
-int k_posconv_prepare_t(const float* g, const float* v, OT* w_fwd, OT* w_bwd, float* norms, int H, int G, int K,
-                        hipStream_t st) {
-  SSAK_REQUIRE(K <= 1024 && H % G == 0 && ((H / G) & 7) == 0, "posconv: K=%d <= 1024 and (H/G)=%d %% 8 == 0 required", K, H / G);
-  const int cg = H / G;
-  // norms layout: [K] ||v||^2 | [K] dot scratch | [H][K] per-workgroup partials
-  float* partial = norms + 2 * K;
-  ProfScope prof_scope(PROF_POSCONV_W, (double)H * cg * K * 8.0, st);  // v read (fp32), two bf16 layouts written
-  posconv_colnorm_kernel<<<H, ((K + 63) / 64) * 64, 0, st>>>(v, nullptr, H / cg, K, cg, partial);  // H = groups * cg workgroups
-  SSAK_LAUNCH_CHECK();
-  posconv_colnorm_finalize_kernel<<<ssak_cdiv(K, 64), 1024, 0, st>>>(partial, H, K, norms);
-  SSAK_LAUNCH_CHECK();
-  SSAK_REQUIRE((size_t)cg * (K + 1) * sizeof(float) <= 64 * 1024, "posconv: (H/G) x K slab does not fit in LDS");
-  posconv_materialize_kernel<OT><<<2 * H, 256, (size_t)cg * (K + 1) * sizeof(float), st>>>(g, v, norms, w_fwd, w_bwd, H, cg, K);
-  SSAK_LAUNCH_CHECK();
-  return SSAK_OK;
-}
-
-int k_posconv_weight_bwd(const float* dw, const float* g, const float* v, const float* norms, float* dg, float* dv,
-                         int H, int G, int K, hipStream_t st) {
-  // `dg` doubles as the scratch for dot[k] would alias the output; use the tail of `norms` (2K floats allocated)
-  const int cg = H / G;
-  float* dot = const_cast<float*>(norms) + K;
-  float* partial = const_cast<float*>(norms) + 2 * K;
-  ProfScope prof_scope(PROF_POSCONV_W, (double)H * cg * K * 12.0, st);  // dw and v read, dv written (fp32)
-  posconv_colnorm_kernel<<<H, ((K + 63) / 64) * 64, 0, st>>>(v, dw, H / cg, K, cg, partial);
-  SSAK_LAUNCH_CHECK();
-  posconv_colnorm_finalize_kernel<<<ssak_cdiv(K, 64), 1024, 0, st>>>(partial, H, K, dot);
-  SSAK_LAUNCH_CHECK();
-  SSAK_REQUIRE((size_t)K * (cg + 1) * sizeof(float) <= 64 * 1024, "posconv: K x (H/G) slab does not fit in LDS");
-  posconv_wbwd_kernel<<<H, 256, (size_t)K * (cg + 1) * sizeof(float), st>>>(dw, g, v, norms, dot, dg, dv, H, cg, K);
-  SSAK_LAUNCH_CHECK();
-  return SSAK_OK;
-}
-
-template <typename T>
-int k_posconv_pack_t(const T* h, T* pg, int B, int F, int H, int G, int K, hipStream_t st) {
-  const int lead = K / 2, RS = F + K;
-  const long rows_total = lead + (long)B * RS + K;
-  const long n = rows_total * G * (H / G / 8);
-  ProfScope prof_scope(PROF_ROWWISE, (double)B * F * H * 2.0 * sizeof(T), st);
-  posconv_pack_kernel<T><<<min(4096, ssak_cdiv(n, 256)), 256, 0, st>>>(h, pg, B, F, H, G, lead, RS, rows_total);
   SSAK_LAUNCH_CHECK();
   return SSAK_OK;
 }
@@ -952,8 +745,6 @@ int k_conv0_gn_gelu_bwd_t(const float* x, const float* w, const float* gamma, co
                                     int, int, hipStream_t, bool);                                                              \
   template int k_conv0_bias_t<T>(const float*, const float*, const float*, T*, int, int, int, int, int, int, hipStream_t);     \
   template int k_conv_weight_rearrange_t<T>(const float*, T*, int, int, int, hipStream_t);                                     \
-  template int k_posconv_prepare_t<T>(const float*, const float*, T*, T*, float*, int, int, int, hipStream_t);                 \
-  template int k_posconv_pack_t<T>(const T*, T*, int, int, int, int, int, hipStream_t);                                        \
   template int k_col2im_t<T>(const T*, T*, int, int, int, int, int, int, hipStream_t);                                        \
   template int k_conv0_wgrad_t<T>(const T*, const float*, float*, float*, int, int, int, int, int, int, hipStream_t);         \
   template int k_conv0_gn_gelu_bwd_t<T>(const float*, const float*, const float*, const float*, const T*, const double*,      \
@@ -971,7 +762,7 @@ extern "C" int ssak_conv0_gn_gelu(const float* x, const float* w, const float* g
   return k_conv0_gn_gelu_t<bf16>(x, w, gamma, beta, (bf16*)out_bf16, (double*)workspace, B, T, T0, C, KS0, ST0, (hipStream_t)stream, false);
 }
 // the same on RAW full-length waveforms: the feature extractor's zero-mean / unit-variance normalisation (a1) folded into the
-// GroupNorm statistics (conv_frontend.hip: NMOM) -- out == ssak_conv0_gn_gelu(ssak_wave_normalize(x)) to fp32 rounding
+// GroupNorm statistics (NMOM above) -- out == ssak_conv0_gn_gelu(ssak_wave_normalize(x)) to fp32 rounding
 extern "C" int ssak_conv0_gn_gelu_raw(const float* x, const float* w, const float* gamma, const float* beta, void* out_bf16, void* workspace,
                                       size_t workspace_bytes, int B, int T, int C, void* stream) {
   SSAK_REQUIRE(x && w && gamma && beta && out_bf16 && workspace, "conv0_gn_gelu_raw: null pointer");
@@ -983,36 +774,6 @@ extern "C" int ssak_conv0_gn_gelu_raw(const float* x, const float* w, const floa
 extern "C" size_t ssak_conv0_workspace_bytes(int B, int T, int C) {
   if (T < KS0) return 0;
   return k_conv0_stats_doubles(B, (T - KS0) / ST0 + 1, C) * sizeof(double);
-}
-
-// ---- debug: the positional convolution's weight preparation, packing and weight-norm backward, one call each
-// (tests/test_gpu_posconv.py; the direct kernels' entries are in posconv.hip).  Nothing on the hot path calls these.
-namespace {
-bool pc_debug_shape(int H, int G, int K) { return H > 0 && G > 0 && K > 0 && K <= 1024 && H % G == 0 && ((H / G) & 7) == 0; }
-}  // namespace
-
-extern "C" int ssak_debug_posconv_prepare(const float* g, const float* v, void* wf, void* wb, float* norms, int H, int G, int K, int dtype,
-                                          void* stream) {
-  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_posconv_prepare: dtype %d (0 bf16, 1 fp32)", dtype);
-  SSAK_REQUIRE(g && v && wf && wb && norms, "debug_posconv_prepare: null pointer");
-  SSAK_REQUIRE(pc_debug_shape(H, G, K), "debug_posconv_prepare: H=%d G=%d K=%d", H, G, K);
-  if (dtype == 0) return k_posconv_prepare_t<bf16>(g, v, (bf16*)wf, (bf16*)wb, norms, H, G, K, (hipStream_t)stream);
-  return k_posconv_prepare_t<float>(g, v, (float*)wf, (float*)wb, norms, H, G, K, (hipStream_t)stream);
-}
-
-extern "C" int ssak_debug_posconv_pack(const void* h, void* pg, int B, int F, int H, int G, int K, int dtype, void* stream) {
-  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_posconv_pack: dtype %d (0 bf16, 1 fp32)", dtype);
-  SSAK_REQUIRE(h && pg, "debug_posconv_pack: null pointer");
-  SSAK_REQUIRE(B > 0 && F > 0 && pc_debug_shape(H, G, K), "debug_posconv_pack: B=%d F=%d H=%d G=%d K=%d", B, F, H, G, K);
-  if (dtype == 0) return k_posconv_pack_t<bf16>((const bf16*)h, (bf16*)pg, B, F, H, G, K, (hipStream_t)stream);
-  return k_posconv_pack_t<float>((const float*)h, (float*)pg, B, F, H, G, K, (hipStream_t)stream);
-}
-
-extern "C" int ssak_debug_posconv_weight_bwd(const float* dwf, const float* g, const float* v, float* norms, float* dg, float* dv, int H,
-                                             int G, int K, void* stream) {
-  SSAK_REQUIRE(dwf && g && v && norms && dg && dv, "debug_posconv_weight_bwd: null pointer");
-  SSAK_REQUIRE(pc_debug_shape(H, G, K), "debug_posconv_weight_bwd: H=%d G=%d K=%d", H, G, K);
-  return k_posconv_weight_bwd(dwf, g, v, norms, dg, dv, H, G, K, (hipStream_t)stream);
 }
 
 // ---- debug: the kernels that run only when the feature encoder trains (--no_freeze), one launch function each

@@ -374,20 +374,9 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 // reads it back; leaving those lines in the XCD's L2 (a plain store does) pushes the operand panels out, which the next
 // tiles then fetch again.  Same-box A/B of the train step (profiles/r03_ab_epilogue_store_policy.log, three alternations):
 // plain 2 019 / 2 023, `nt` 2 031 / 2 033 utterances/s (+0.5 %: the N = 768 forward products 1 991 -> 1 958 us per step);
-// write-through `sc1` stores 1 890 (-6.5 %: every store a fabric write of its own).  -DSSAK_EPI_STORE=0 / 1 build the plain /
-// sc1 forms.
-#ifndef SSAK_EPI_STORE
-#define SSAK_EPI_STORE 2
-#endif
-__device__ __forceinline__ void epi_store16(void* dst, u32x4 v) {
-#if SSAK_EPI_STORE == 1
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(v) : "memory");
-#elif SSAK_EPI_STORE == 2
-  __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(dst));
-#else
-  *reinterpret_cast<u32x4*>(dst) = v;
-#endif
-}
+// write-through `sc1` stores 1 890 (-6.5 %: every store a fabric write of its own).  The plain store and the `sc1` store were
+// rejected on those figures; only the non-temporal form is built.
+__device__ __forceinline__ void epi_store16(void* dst, u32x4 v) { __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(dst)); }
 // store 16 rows x 64 columns of codes held as g[j][r] (accumulator layout) at dst + row lm, + 16 * lq: one 16-byte store per lane
 __device__ __forceinline__ void store_fq_rows(uint8_t* dst_lane, const float (&g)[4][4], bool rowok) {
   uint32_t q[4];

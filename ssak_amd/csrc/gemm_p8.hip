@@ -96,12 +96,6 @@ struct P8Stager {
   // stage piece `h` of k-tile kt (absolute index; kt >= kt_end: zero-writing dummies) and advance that piece's offsets
   template <int H>
   __device__ __forceinline__ void issue(char* lds_piece, int kt, int kt_end, int K, int perm_p = 0, int perm_n2 = 0) {
-#if defined(P8_ABL) && (P8_ABL & 1)
-    if (kt >= 2) return;  // ablation: no LDS-DMA inside the main loop
-#endif
-#if defined(P8_ABL) && (P8_ABL & 32)
-    if (NSEG == 4 && kt >= 2) return;  // ablation: no LDS-DMA of the B operand inside the main loop
-#endif
     // k-rows / k-chunks of this tile that exist (uniform): all 64, a K tail, or none (dummy past the last tile)
     const int klim = kt < kt_end ? min(K - kt * BK, BK) : 0;
     // advance to the next K tile of the visiting order: step kt -> kt + 1 moves by + p (even step of a pair), 1 - p (odd) or 1
@@ -119,7 +113,7 @@ struct P8Stager {
 };
 
 // per-lane fragment offsets inside a piece; w0 = first piece row of this wave's panel, NF 16-row groups
-template <bool KM, int NF, bool IS_B = false>
+template <bool KM, int NF>
 struct P8Frag {
   int off[KM ? NF : 1];
   __device__ __forceinline__ void init(int w0, int lane) {
@@ -137,19 +131,14 @@ struct P8Frag {
     }
   }
   __device__ __forceinline__ bf16x8 read(const char* piece, int i, int kk) const {
-#if defined(P8_ABL) && (P8_ABL & 2)
-    return __builtin_bit_cast(bf16x8, (f32x4){(float)i, (float)kk, 1.f, 2.f});  // ablation: no fragment reads
-#endif
-#if defined(P8_ABL) && (P8_ABL & 16)
-    if (IS_B) return __builtin_bit_cast(bf16x8, (f32x4){(float)i, (float)kk, 1.f, 2.f});  // ablation: no B fragment reads
-#endif
     if (!KM) {
       return *reinterpret_cast<const bf16x8*>(piece + ((off[0] ^ (kk << 6)) + i * 2048));
     } else {
       // inline asm on purpose: for the ds_read_tr builtin the compiler cannot tell the read apart from the LDS-DMA writes
       // in flight and puts `s_waitcnt vmcnt(0)` in front of every fragment read, which drains the whole pipeline four
       // times per K tile.  Ordering is by the counted waits + barriers of the phase structure; results are consumed
-      // after the explicit lgkmcnt(0) of P8_MFMA.
+      // after the explicit `s_waitcnt lgkmcnt(0)` that every load phase of the main loop issues in front of the barrier
+      // that closes it.
       typedef __attribute__((address_space(3))) char lds_char;
       const uint32_t a = (uint32_t)(uintptr_t)(lds_char*)(piece + off[KM ? i : 0] + kk * 32 * 256);
       s16x4 lo, hi;
@@ -162,45 +151,12 @@ struct P8Frag {
   }
 };
 
-// development aid (tools/probes/p8_probe.hip): per-workgroup wall-clock stamps written through p.slab
-#ifdef P8_STAMPS
-#define P8_STAMP(i)                                                                                   \
-  do {                                                                                                \
-    if (threadIdx.x == 0) reinterpret_cast<unsigned long long*>(p.slab)[(blockIdx.x * 4 + p8_round) * 8 + (i)] = wall_clock64(); \
-  } while (0)
-#else
-#define P8_STAMP(i)
-#endif
-
 #define P8_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define P8_BARRIER()                \
   do {                              \
     P8_FENCE();                     \
     __builtin_amdgcn_s_barrier();   \
     P8_FENCE();                     \
-  } while (0)
-// the 4 * MH MFMAs of one output quadrant: 16-row groups I0..I0+MH-1 x column groups J0, J0+1, both 32-deep halves
-#if defined(P8_ABL) && (P8_ABL & 4)
-#define P8_MFMA_BODY(I0, J0, FB) acc[(I0)][(J0)] += (f32x4){(float)FB[0][0][0], (float)fa[0][0][0], 0.f, 0.f}; /* ablation: no MFMAs */
-#else
-#define P8_MFMA_BODY(I0, J0, FB)                                                                              \
-    _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) _Pragma("unroll") for (int i = 0; i < MH; ++i)           \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[(I0) + i][(J0) + j] =                               \
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(FB[j][kk], fa[i][kk], acc[(I0) + i][(J0) + j], 0, 0, 0);
-#endif
-#if defined(P8_ABL) && (P8_ABL & 8)
-#define P8_LOOP_BARRIER() P8_FENCE() /* ablation: no barriers inside the main loop */
-#else
-#define P8_LOOP_BARRIER() P8_BARRIER()
-#endif
-#define P8_MFMA(I0, J0, FB)                                                                                   \
-  do {                                                                                                        \
-    P8_LOOP_BARRIER();                                                                                        \
-    __builtin_amdgcn_s_waitcnt(0xc07f); /* lgkmcnt(0) */                                                      \
-    __builtin_amdgcn_s_setprio(1);                                                                            \
-    P8_MFMA_BODY(I0, J0, FB)                                                                                  \
-    __builtin_amdgcn_s_setprio(0);                                                                            \
-    P8_LOOP_BARRIER();                                                                                        \
   } while (0)
 
 // MH = 16-row groups per quadrant: the tile is (64 * MH) x 256, i.e. 256 / 192 / 128 rows -- picked by the host so
@@ -243,9 +199,6 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_p8_kernel(const GemmParams p,
   // and BR staged from LA, so that both load phases carry 2 MH + 4 fragment reads and 4 LDS-DMA instructions instead of
   // 2 MH + 8 / 2 and 2 MH / 6 -- were built in round 3, bit-identical, and are 3-10 % SLOWER: profiles/r03_gemm_balanced_probe.log.)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef P8_STAMPS
-  int p8_round = 0;  // stamps: [workgroup][tile round < 4][8]
-#endif
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wr = wave >> 2, wc = wave & 3;
@@ -291,7 +244,7 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_p8_kernel(const GemmParams p,
   P8Stager<A_KM, SEGA, 2 * SEGA, A_KM ? 16 : 4 * MH, 2> sa;
   P8Stager<B_KM, 32, 64, 16, 4> sb;
   P8Frag<A_KM, MH> fra;
-  P8Frag<B_KM, 2, true> frb;
+  P8Frag<B_KM, 2> frb;
   fra.init(wr * SEGA, lane);
   frb.init(wc * 32, lane);
   // piece slots of buffer b: AT = 0, AB = 1, BL = 2, BR = 3
@@ -369,7 +322,6 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_p8_kernel(const GemmParams p,
   P8Tile cur_t = decode(min(t_first, ntiles - 1));
   for (int t = t_first; t < ntiles;) {
     const P8Tile c = cur_t;
-    P8_STAMP(0);
     const bool was_primed = primed;
     if (!primed) {
       prime(c);
@@ -383,7 +335,6 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_p8_kernel(const GemmParams p,
     }
     P8_BARRIER();     // ... everyone's
     if (wr == 1) P8_BARRIER();  // wave row 1 runs one barrier behind wave row 0
-    P8_STAMP(1);
     if (tile_ctr && threadIdx.x == 0) ticket = atomicAdd(tile_ctr, 1);  // next tile's ticket: retires under the main loop
 
     f32x4 acc[2 * MH][4];
@@ -457,7 +408,6 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_p8_kernel(const GemmParams p,
     }
     if (wr == 0) P8_BARRIER();
     wait_vmcnt<0>();  // drain the trailing dummies before LDS is released
-    P8_STAMP(2);
     if (tile_ctr && threadIdx.x == 0) *ticket_lds = ticket;
 
     __syncthreads();  // DMA drained in every wave, all fragment reads done: LDS is free
@@ -498,15 +448,6 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_p8_kernel(const GemmParams p,
       gemm_epilogue<MH, 4>(pe, reinterpret_cast<f32x4(&)[MH][4]>(acc[MH]), bias_regs, lds_wave, c.bm0, c.bn0, wr * 2 * SEGA + SEGA, wc * 64, lane, c.z, c.z1, c.z2, c.split);
       __syncthreads();  // the transposition buffers are read out before the next tile's pieces overwrite them
     }
-    P8_STAMP(3);
-#ifdef P8_STAMPS
-    __syncthreads();
-    P8_STAMP(4);  // every wave has issued its epilogue
-    wait_vmcnt<0>();
-    __syncthreads();
-    P8_STAMP(5);  // ... and its stores have drained
-    p8_round = min(p8_round + 1, 3);
-#endif
     t = t_next;
   }
   // the last workgroup out leaves the counters at zero for the next launch on this stream
@@ -640,9 +581,6 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_p8bd_kernel(const GemmParams 
   // fragments of column groups 2 * HALF, 2 * HALF + 1 (HALF = 2: all four) of the K tile visited at `step`
   auto load_b = [&](bf16x8(&dst)[4][2], int step, auto half_tag) {
     constexpr int HALF = decltype(half_tag)::value;
-#if defined(P8BD_ABL) && (P8BD_ABL & 1)
-    if (step >= 2) return;  // ablation: no B loads inside the main loop
-#endif
     int kta = step < 2 * kpn ? (step >> 1) + ((step & 1) ? kpp : 0) : step - kpn;  // K tile of this step (P8Stager::issue's order)
     kta = min(kta, nkt - 1);                                                         // past the end: a valid tile nobody uses
     const uint32_t so = b_col + (uint32_t)kta * 8192u;
@@ -739,11 +677,7 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_p8bd_kernel(const GemmParams 
         if (epi_vm == 8 * MH) wait_vmcnt<8 + 8 * MH>();
         else wait_vmcnt<8 + 4 * MH>();
       } else {
-#if defined(P8BD_ABL) && (P8BD_ABL & 1)
-        wait_vmcnt<4>();
-#else
         wait_vmcnt<8>();
-#endif
       }
       __builtin_amdgcn_s_waitcnt(0xc07f);  // this wave's fragment reads are done
       P8_BARRIER();

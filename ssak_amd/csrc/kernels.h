@@ -41,7 +41,7 @@ struct DropSpec {
 // encoder layers) the producers queue the job instead and k_reduce_flush runs all of them as ONE launch; the partial buffers
 // must stay untouched until then.
 // reduce_jobs_kernel (norm_act.hip) is the one kernel of this shape.  The remaining second stages are other sums: the
-// positional convolution's posconv_colnorm_finalize_kernel (conv_frontend.hip) ASSIGNS its total; the slab sums of the
+// positional convolution's posconv_colnorm_finalize_kernel (posconv.hip) ASSIGNS its total; the slab sums of the
 // --no_freeze feature-encoder backward (sum_slabs_kernel, conv0_wgrad_sum_kernel, conv0_bwd_dw_kernel) add sequentially and
 // sb_head.hip totals in double precision, so their bits would change under this summation order.
 struct ReduceJob {
@@ -140,13 +140,6 @@ int k_conv0_gn_gelu_bwd_t(const float* x, const float* w, const float* gamma, co
                         hipStream_t st);
 template <typename T>
 int k_conv_weight_rearrange_t(const float* w, T* out, int Co, int Ci, int k, hipStream_t st);
-template <typename T>
-int k_posconv_prepare_t(const float* g, const float* v, T* w_fwd, T* w_bwd, float* norms, int H, int G, int K,
-                        hipStream_t st);
-int k_posconv_weight_bwd(const float* dw, const float* g, const float* v, const float* norms, float* dg, float* dv,
-                         int H, int G, int K, hipStream_t st);
-template <typename T>
-int k_posconv_pack_t(const T* h, T* pg, int B, int F, int H, int G, int K, hipStream_t st);
 
 // attn_adapter.hip: the closing row kernel of a stable-LN layer with an MMS language adapter, one launch:
 // r2 = res + y (y may be null), r2' = r2 + W2 relu(W1 LN_a(r2) + b1) + b2 -> r_out (may alias res / y), LN_next(r2') -> out
@@ -178,6 +171,16 @@ int k_posconv_direct(const bf16* x, long rows_per_group, int row0, const bf16* w
 size_t k_posconv_wgrad_scratch_floats(int H, int G, int K);
 int k_posconv_wgrad_direct(const bf16* x, const bf16* dy, long rows_per_group, long rows, int lead, float* dwf, float* scratch, int H, int G,
                            int K, hipStream_t st);
+
+// ... and the weight plumbing: w = g v / ||v|| in the layouts the products read (norms: 2 K + H K floats of scratch), its backward
+// to (g, v), and the zero-padded per-group packing of the activations
+template <typename T>
+int k_posconv_prepare_t(const float* g, const float* v, T* w_fwd, T* w_bwd, float* norms, int H, int G, int K,
+                        hipStream_t st);
+int k_posconv_weight_bwd(const float* dw, const float* g, const float* v, const float* norms, float* dg, float* dv,
+                         int H, int G, int K, hipStream_t st);
+template <typename T>
+int k_posconv_pack_t(const T* h, T* pg, int B, int F, int H, int G, int K, hipStream_t st);
 
 // whisper_frontend.hip
 // (T_ = bf16, or float in the fp32-exact mode)

@@ -14,7 +14,8 @@
 //     channels 8 (q % 6);  cg = 64 (XLSR-large): a step = 1 tap = 64 k = 2 slices, chunk q -> channels 8 q.
 //   LDS row pitch 96 B (cg = 48) / 160 B (cg = 64): conflict-free ds_read_b128 fragments (see PcGeom::PITCH).
 // Serves the forward (bias + GELU, pre-activation saved) and the input gradient (flipped taps prepared by k_posconv_prepare,
-// plain store); the weight gradient (contraction over time) is posconv_wgrad_kernel further down.
+// plain store); the weight gradient (contraction over time) is posconv_wgrad_kernel further down.  Behind them: the weight
+// plumbing (weight-norm materialisation and its backward, activation packing) that feeds these kernels.
 #include <algorithm>
 
 #include "common.h"
@@ -457,6 +458,189 @@ int k_posconv_wgrad_direct(const bf16* x, const bf16* dy, long rows_per_group, l
   return SSAK_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Weight plumbing: weight_norm(dim=2) materialisation w = g v / ||v|| into the forward GEMM layout [H][K][H/G] and the
+// flipped / transposed layout of the input-gradient product, its backward to (g, v), and the zero-padded per-group packing of
+// the activations that the direct kernels above read.
+namespace {
+
+// Per-tap sums over the [H][cg] rows of v[o][c][k] (k fastest): ||v_k||^2, or the dot product with the weight gradient
+// dwf[group][k][c][n] (o = group * cg + n).  One workgroup per (group, c) pair, a thread per tap k: the reads of v are
+// coalesced over k, each thread walks the cg contiguous n of its dwf row; partial[(group * cg + c)][k], then a fixed-order
+// reduction.  (The first version used 256 two-wave workgroups striding over all rows with an uncoalesced dwf gather and a
+// single-workgroup serial finalize: 89 + 60 us for 19 MB.)
+__global__ void posconv_colnorm_kernel(const float* __restrict__ v, const float* __restrict__ dwf, int G, int K, int cg,
+                                       float* __restrict__ partial) {
+  const int k = threadIdx.x;
+  if (k >= K) return;
+  const int g = blockIdx.x / cg, c = blockIdx.x % cg;
+  float s = 0.f;
+  const float* vp = v + ((long)(g * cg) * cg + c) * K + k;  // + n * cg * K
+  if (dwf) {
+    const float* dp = dwf + (((long)g * K + k) * cg + c) * cg;  // + n
+    // (unrolled: the loads of eight rows in flight per thread; one at a time this kernel ran at HBM latency, 34 us for 19 MB)
+#pragma unroll 8
+    for (int n = 0; n < cg; ++n) s = fmaf(vp[(long)n * cg * K], dp[n], s);
+  } else {
+#pragma unroll 8
+    for (int n = 0; n < cg; ++n) {
+      const float a = vp[(long)n * cg * K];
+      s = fmaf(a, a, s);
+    }
+  }
+  partial[(size_t)blockIdx.x * K + k] = s;
+}
+// out[k] = sum over nblk partial rows, fixed order; workgroup = 64 taps x 16 row groups
+__global__ __launch_bounds__(1024) void posconv_colnorm_finalize_kernel(const float* __restrict__ partial, int nblk, int K, float* __restrict__ out) {
+  __shared__ float red[16][65];
+  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+  const int k = blockIdx.x * 64 + cx;
+  float s = 0.f;
+  if (k < K) {
+#pragma unroll 8
+    for (int b = ry; b < nblk; b += 16) s += partial[(size_t)b * K + k];  // (eight loads in flight: two workgroups do all of it)
+  }
+  red[ry][cx] = s;
+  __syncthreads();
+  if (ry == 0 && k < K) {
+    float t = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t += red[r][cx];
+    out[k] = t;
+  }
+}
+
+// w = g[k] v / ||v_k|| in the two bf16 layouts the GEMMs read: wf[o][k][c] (forward / dX operand) and
+// wb[group][c][K-1-k][n] (o = group * cg + n).  Both are (c, k) <-> (k, c|n) transposes of v[o][c][k]: a workgroup stages
+// one [cg][K] slab through LDS -- slab o for wf (blocks [0, H)), the slab of (group, c) over its cg output channels for wb
+// (blocks [H, 2H)) -- so that global reads and writes are both contiguous (the element-wise version scattered 2-byte
+// stores: 48 us for 38 MB).
+template <typename OT>
+__global__ __launch_bounds__(256) void posconv_materialize_kernel(const float* __restrict__ g, const float* __restrict__ v,
+                                                                  const float* __restrict__ nsq, OT* __restrict__ wf,
+                                                                  OT* __restrict__ wb, int H, int cg, int K) {
+  extern __shared__ float slab[];  // [cg][K + 1]
+  const int KP = K + 1;
+  const bool back = (int)blockIdx.x >= H;
+  const int id = back ? blockIdx.x - H : blockIdx.x;
+  if (!back) {
+    const float* src = v + (long)id * cg * K;  // v[o = id][c][k]
+    for (int j = threadIdx.x; j < cg * K; j += 256) {
+      const int c = j / K, k = j % K;
+      slab[c * KP + k] = g[k] * src[j] * rsqrtf(nsq[k]);
+    }
+    __syncthreads();
+    OT* dst = wf + (long)id * K * cg;  // wf[o][k][c]
+    for (int j = threadIdx.x; j < K * cg; j += 256) dst[j] = (OT)slab[(j % cg) * KP + j / cg];
+  } else {
+    const int grp = id / cg, c = id % cg;
+    for (int j = threadIdx.x; j < cg * K; j += 256) {
+      const int nn = j / K, k = j % K;
+      slab[nn * KP + k] = g[k] * v[(((long)grp * cg + nn) * cg + c) * K + k] * rsqrtf(nsq[k]);
+    }
+    __syncthreads();
+    OT* dst = wb + (long)id * K * cg;  // wb[group][c][kk][n], kk = K - 1 - k
+    for (int j = threadIdx.x; j < K * cg; j += 256) dst[j] = (OT)slab[(j % cg) * KP + (K - 1 - j / cg)];
+  }
+}
+
+// weight-norm backward: dv[o][c][k] += g[k] / ||v_k|| (d - v dot[k] / ||v_k||^2), dg[k] += dot[k] / ||v_k||, with
+// d = dwf[group][k][c][n].  One workgroup per (group, c): the dwf rows (contiguous over n) go through LDS and leave
+// as rows contiguous over k.
+__global__ __launch_bounds__(256) void posconv_wbwd_kernel(const float* __restrict__ dwf, const float* __restrict__ g,
+                                                           const float* __restrict__ v, const float* __restrict__ nsq,
+                                                           const float* __restrict__ dot, float* __restrict__ dg,
+                                                           float* __restrict__ dv, int H, int cg, int K) {
+  extern __shared__ float slab[];  // [K][cg + 1]
+  const int CP = cg + 1;
+  const int grp = blockIdx.x / cg, c = blockIdx.x % cg;
+  for (int j = threadIdx.x; j < K * cg; j += 256) {
+    const int k = j / cg, nn = j % cg;
+    slab[k * CP + nn] = dwf[(((long)grp * K + k) * cg + c) * cg + nn];
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < cg * K; j += 256) {
+    const int nn = j / K, k = j % K;
+    const long e = (((long)grp * cg + nn) * cg + c) * K + k;
+    const float inv = rsqrtf(nsq[k]);
+    dv[e] += g[k] * inv * (slab[k * CP + nn] - v[e] * dot[k] * inv * inv);
+  }
+  if (blockIdx.x == 0)
+    for (int k = threadIdx.x; k < K; k += 256) dg[k] += dot[k] * rsqrtf(nsq[k]);
+}
+
+template <typename T>
+__global__ void posconv_pack_kernel(const T* __restrict__ h, T* __restrict__ pg, int B, int F, int H, int G,
+                                    int lead, int RS, long rows_total) {
+  const int cg = H / G, cpr = cg >> 3;
+  const long n = rows_total * G * cpr;
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+    const int cc = (int)(e % cpr);
+    const long r = (e / cpr) % rows_total;
+    const int g = (int)(e / ((long)cpr * rows_total));
+    const long rr = r - lead;
+    Chunk8<T> val = {};
+    if (rr >= 0) {
+      const int b = (int)(rr / RS), t = (int)(rr % RS);
+      if (b < B && t < F) val = ld8<T>(h + ((long)b * F + t) * H + g * cg + cc * 8);
+    }
+    st8<T>(pg + ((long)g * rows_total + r) * cg + cc * 8, val);
+  }
+}
+
+}  // namespace
+
+template <typename OT>
+int k_posconv_prepare_t(const float* g, const float* v, OT* w_fwd, OT* w_bwd, float* norms, int H, int G, int K,
+                        hipStream_t st) {
+  SSAK_REQUIRE(K <= 1024 && H % G == 0 && ((H / G) & 7) == 0, "posconv: K=%d <= 1024 and (H/G)=%d %% 8 == 0 required", K, H / G);
+  const int cg = H / G;
+  // norms layout: [K] ||v||^2 | [K] dot scratch | [H][K] per-workgroup partials
+  float* partial = norms + 2 * K;
+  ProfScope prof_scope(PROF_POSCONV_W, (double)H * cg * K * 8.0, st);  // v read (fp32), two bf16 layouts written
+  posconv_colnorm_kernel<<<H, ((K + 63) / 64) * 64, 0, st>>>(v, nullptr, H / cg, K, cg, partial);  // H = groups * cg workgroups
+  SSAK_LAUNCH_CHECK();
+  posconv_colnorm_finalize_kernel<<<ssak_cdiv(K, 64), 1024, 0, st>>>(partial, H, K, norms);
+  SSAK_LAUNCH_CHECK();
+  SSAK_REQUIRE((size_t)cg * (K + 1) * sizeof(float) <= 64 * 1024, "posconv: (H/G) x K slab does not fit in LDS");
+  posconv_materialize_kernel<OT><<<2 * H, 256, (size_t)cg * (K + 1) * sizeof(float), st>>>(g, v, norms, w_fwd, w_bwd, H, cg, K);
+  SSAK_LAUNCH_CHECK();
+  return SSAK_OK;
+}
+
+int k_posconv_weight_bwd(const float* dw, const float* g, const float* v, const float* norms, float* dg, float* dv,
+                         int H, int G, int K, hipStream_t st) {
+  // `dg` doubles as the scratch for dot[k] would alias the output; use the tail of `norms` (2K floats allocated)
+  const int cg = H / G;
+  float* dot = const_cast<float*>(norms) + K;
+  float* partial = const_cast<float*>(norms) + 2 * K;
+  ProfScope prof_scope(PROF_POSCONV_W, (double)H * cg * K * 12.0, st);  // dw and v read, dv written (fp32)
+  posconv_colnorm_kernel<<<H, ((K + 63) / 64) * 64, 0, st>>>(v, dw, H / cg, K, cg, partial);
+  SSAK_LAUNCH_CHECK();
+  posconv_colnorm_finalize_kernel<<<ssak_cdiv(K, 64), 1024, 0, st>>>(partial, H, K, dot);
+  SSAK_LAUNCH_CHECK();
+  SSAK_REQUIRE((size_t)K * (cg + 1) * sizeof(float) <= 64 * 1024, "posconv: K x (H/G) slab does not fit in LDS");
+  posconv_wbwd_kernel<<<H, 256, (size_t)K * (cg + 1) * sizeof(float), st>>>(dw, g, v, norms, dot, dg, dv, H, cg, K);
+  SSAK_LAUNCH_CHECK();
+  return SSAK_OK;
+}
+
+template <typename T>
+int k_posconv_pack_t(const T* h, T* pg, int B, int F, int H, int G, int K, hipStream_t st) {
+  const int lead = K / 2, RS = F + K;
+  const long rows_total = lead + (long)B * RS + K;
+  const long n = rows_total * G * (H / G / 8);
+  ProfScope prof_scope(PROF_ROWWISE, (double)B * F * H * 2.0 * sizeof(T), st);
+  posconv_pack_kernel<T><<<min(4096, ssak_cdiv(n, 256)), 256, 0, st>>>(h, pg, B, F, H, G, lead, RS, rows_total);
+  SSAK_LAUNCH_CHECK();
+  return SSAK_OK;
+}
+
+template int k_posconv_prepare_t<bf16>(const float*, const float*, bf16*, bf16*, float*, int, int, int, hipStream_t);
+template int k_posconv_prepare_t<float>(const float*, const float*, float*, float*, float*, int, int, int, hipStream_t);
+template int k_posconv_pack_t<bf16>(const bf16*, bf16*, int, int, int, int, int, hipStream_t);
+template int k_posconv_pack_t<float>(const float*, float*, int, int, int, int, int, hipStream_t);
+
 // ---- debug: the direct kernels of this file, one stage each (tests/test_gpu_posconv.py holds them to the float64 restatement
 // tests/posconv_ref.py).  The same pack / fragment / launch functions the engine calls (w2v2_engine.hip, a6 and its backward), with
 // the engine's packed geometry; the caller's workspace takes the place of the engine's arena.  Nothing on the hot path calls these.
@@ -520,4 +704,34 @@ extern "C" int ssak_debug_posconv_wgrad(const void* h, const void* dpre, float* 
   rc = k_posconv_pack_t<bf16>((const bf16*)dpre, pdy, B, F, H, G, K, st);
   if (rc != SSAK_OK) return rc;
   return k_posconv_wgrad_direct(px, pdy, ws.rows_per_group, (long)B * (F + K), K / 2, dwf, (float*)(base + ws.scratch), H, G, K, st);
+}
+
+// ---- debug: the positional convolution's weight preparation, packing and weight-norm backward, one call each
+// (tests/test_gpu_posconv.py; the direct kernels' entries are above).  Nothing on the hot path calls these.
+namespace {
+bool pc_debug_shape(int H, int G, int K) { return H > 0 && G > 0 && K > 0 && K <= 1024 && H % G == 0 && ((H / G) & 7) == 0; }
+}  // namespace
+
+extern "C" int ssak_debug_posconv_prepare(const float* g, const float* v, void* wf, void* wb, float* norms, int H, int G, int K, int dtype,
+                                          void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_posconv_prepare: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(g && v && wf && wb && norms, "debug_posconv_prepare: null pointer");
+  SSAK_REQUIRE(pc_debug_shape(H, G, K), "debug_posconv_prepare: H=%d G=%d K=%d", H, G, K);
+  if (dtype == 0) return k_posconv_prepare_t<bf16>(g, v, (bf16*)wf, (bf16*)wb, norms, H, G, K, (hipStream_t)stream);
+  return k_posconv_prepare_t<float>(g, v, (float*)wf, (float*)wb, norms, H, G, K, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_posconv_pack(const void* h, void* pg, int B, int F, int H, int G, int K, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_posconv_pack: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(h && pg, "debug_posconv_pack: null pointer");
+  SSAK_REQUIRE(B > 0 && F > 0 && pc_debug_shape(H, G, K), "debug_posconv_pack: B=%d F=%d H=%d G=%d K=%d", B, F, H, G, K);
+  if (dtype == 0) return k_posconv_pack_t<bf16>((const bf16*)h, (bf16*)pg, B, F, H, G, K, (hipStream_t)stream);
+  return k_posconv_pack_t<float>((const float*)h, (float*)pg, B, F, H, G, K, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_posconv_weight_bwd(const float* dwf, const float* g, const float* v, float* norms, float* dg, float* dv, int H,
+                                             int G, int K, void* stream) {
+  SSAK_REQUIRE(dwf && g && v && norms && dg && dv, "debug_posconv_weight_bwd: null pointer");
+  SSAK_REQUIRE(pc_debug_shape(H, G, K), "debug_posconv_weight_bwd: H=%d G=%d K=%d", H, G, K);
+  return k_posconv_weight_bwd(dwf, g, v, norms, dg, dv, H, G, K, (hipStream_t)stream);
 }

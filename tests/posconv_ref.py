@@ -1,6 +1,6 @@
 """Float64 restatement of the grouped, weight-normed positional convolution of the Wav2Vec2 encoder
 (``Conv1d(H, H, K, padding = K // 2, groups = G)`` under ``weight_norm(dim = 2)``, the last frame dropped for even K, then GELU),
-of its gradients and of the layouts the kernels of ssak_amd/csrc/posconv.hip and conv_frontend.hip exchange.
+of its gradients and of the layouts the kernels of ssak_amd/csrc/posconv.hip exchange.
 
 Written from the definition in plain torch, one tap at a time, and device-agnostic: every function computes where its inputs
 live, so the largest cases run in float64 on the device.  ``tests/test_posconv_ref.py`` pins every function to
@@ -16,7 +16,7 @@ g [K];  bias [H].
     dw[o, c, k]  = sum_{b, t} dpre[b, t, o] h[b, t + k - K // 2, group(o) * cg + c]
     dot[k] = sum_{o, c} dw v,   dg[k] = dot[k] / ||v_k||,   dv = g / ||v_k|| (dw - v dot / ||v_k||^2)
 
-Kernel layouts (index formulas from the comments of conv_frontend.hip / posconv.hip):
+Kernel layouts (index formulas from the comments of posconv.hip):
 
     wf[o][k][c]                = w[o, c, k]                         forward operand
     wb[group][c][K - 1 - k][n] = w[group * cg + n, c, k]            input-gradient operand (flipped taps)

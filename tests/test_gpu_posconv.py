@@ -1,4 +1,4 @@
-"""GPU: the grouped positional convolution (ssak_amd/csrc/posconv.hip and its helpers in conv_frontend.hip), one stage at a time,
+"""GPU: the grouped positional convolution (ssak_amd/csrc/posconv.hip: the direct kernels and their weight plumbing), one stage at a time,
 against the float64 restatement tests/posconv_ref.py (itself pinned to torch's conv1d / weight_norm under float64 autograd by
 tests/test_posconv_ref.py), through the test-only entries ssak_debug_posconv_prepare / _pack / _direct / _wgrad / _weight_bwd.
 The references run in float64 on the device, on exactly the bf16 inputs and bf16 weights the kernels read, so only a kernel's own

@@ -1,8 +1,10 @@
 // Development probe: the persistent 256 x 256 GEMM kernel (lean bf16 epilogue) timed on the train step's shapes, for A/B runs
-// of main-loop variants selected with -D flags in gemm_p8.hip.  Prints us, TFLOP/s and an order-independent checksum of C
-// (two builds that compute the same thing print the same checksum).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Issak_amd/csrc -mllvm -amdgpu-mfma-vgpr-form [-DP8_VARIANT=n]
+// of main-loop ablations (-DP8_ABL=1|2|16|32, -DP8BD_ABL=1: the hooks of tools/probes/p8_hooks.patch.txt).  Prints us, TFLOP/s
+// and an order-independent checksum of C (two builds that compute the same thing print the same checksum).
+//   git apply tools/probes/p8_hooks.patch.txt
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Issak_amd/csrc -mllvm -amdgpu-mfma-vgpr-form [-DP8_ABL=n]
 //         -x hip tools/probes/p8_loop.hip ssak_amd/csrc/api.cpp -o tools/probes/p8_loop_<tag>.bin
+//   git apply -R tools/probes/p8_hooks.patch.txt
 #include "../../ssak_amd/csrc/gemm_p8.hip"
 
 #include <algorithm>

@@ -1,14 +1,15 @@
 // Development probe: per-workgroup wall-clock stamps of gemm_p8_kernel (start / pipeline primed / main loop done /
-// epilogue issued / stores drained) on one shape.  hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude
-//   -Issak_amd/csrc -DP8_STAMPS tools/probes/p8_probe.hip -o build/p8_probe ; ./build/p8_probe M N K
+// epilogue issued / stores drained) on one shape.  The stamps are not in the product source:
+//   git apply tools/probes/p8_hooks.patch.txt
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Issak_amd/csrc -DP8_STAMPS -x hip tools/probes/p8_probe.hip
+//         ssak_amd/csrc/api.cpp -o build/p8_probe
+//   git apply -R tools/probes/p8_hooks.patch.txt ; ./build/p8_probe M N K
 #include "../../ssak_amd/csrc/gemm_p8.hip"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-
-void ssak_set_error(const char*, ...) {}
 
 int main(int argc, char** argv) {
   const int M = argc > 1 ? atoi(argv[1]) : 15968, N = argc > 2 ? atoi(argv[2]) : 2304, K = argc > 3 ? atoi(argv[3]) : 768;
@@ -44,16 +45,14 @@ int main(int argc, char** argv) {
   hipMalloc(&st, (size_t)nblk * 256);
   hipMemset(st, 0, (size_t)nblk * 256);
   p.slab = (float*)st;
-  #ifndef P8_MH
-#define P8_MH 4
-#endif
   auto kern = gemm_p8_kernel<P8_MH, false, false>;
+  const P8GroupT<1> none{};  // ungrouped launch: the problem table is not read
   hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, P8_LDS);
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
   for (int it = 0; it < 3; ++it) {
     hipEventRecord(e0);
-    kern<<<nblk, P8_THREADS, P8_LDS>>>(p);
+    kern<<<nblk, P8_THREADS, P8_LDS>>>(p, none);
     hipEventRecord(e1);
     hipDeviceSynchronize();
   }
