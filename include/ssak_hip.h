@@ -679,8 +679,8 @@ int ssak_cls_softmax_ce(const float* logits, const int32_t* labels, const int32_
  * The decoder of transformers' WhisperForConditionalGeneration as a teacher-forced pass (ssak/infer/whisper_infer.py and
  * ssak/train/transformers/whisper_train.py:498-507 run it): these three entries plus ssak_gemm_bf16 (projections, feed-forward,
  * the vocabulary projection against the tied embedding) and ssak_layernorm_fwd.  Host-side composition:
- * ssak_amd/whisper_seq2seq.py.  bf16 storage, fp32 accumulation; every sum in a fixed order, no float atomics; no backward, so
- * nothing is saved.  No per-kernel timing has been measured (whole calls: tools/bench_whisper_decoder.py).
+ * ssak_amd/whisper_seq2seq.py.  bf16 storage, fp32 accumulation; every sum in a fixed order, no float atomics; nothing is saved (the
+ * backward is ABI 650 below).  No per-kernel timing has been measured (whole calls: tools/bench_whisper_decoder.py).
  *
  * ssak_dec_embed.  out [B * L, D] bf16, out[b, i, :] = bf16(fp32(embed_tokens[ids[b, i], :]) + fp32(embed_positions[pos_offset +
  * i, :])); embed_tokens [V, D] and embed_positions [max_positions, D] bf16, D a multiple of 8, all 16-byte aligned.  ids [B * L]
@@ -850,6 +850,63 @@ int ssak_dec_attention_step_grouped(const void* q, long ldq, const void* k, long
  * 8, <= 1536. */
 int ssak_layernorm_fwd(const void* y, const void* res, const float* gamma, const float* beta, void* r_out, void* out, int M, int C,
                        float eps, int dtype, void* stream);
+
+/* ---- Whisper training (ABI 650): the backward kernels of the text decoder ------------------------------------------------
+ * What ssak/train/transformers/whisper_train.py:498-507,531 (the loss and loss.backward() of WhisperForConditionalGeneration)
+ * needs of the decoder beyond ssak_gemm_bf16 (dgrad, wgrad with a_kmajor + accumulate, colsum, the GELU pair), ssak_cast_f32_bf16,
+ * ssak_grad_sumsq(_add) and ssak_adamw_step.  Conventions of ABI 600: bf16 storage, fp32 accumulation, every sum in a fixed order,
+ * NO FLOAT ATOMICS (two runs give the same bits), host copies validated before any launch (SSAK_ERR_INVALID, nothing launched),
+ * head_dim 64 only.  Timing: tools/bench_whisper_train.py (DESIGN.md "Whisper fine-tuning").
+ *
+ * ssak_dec_attention_fwd_lse.  ssak_dec_attention_fwd plus lse [B, nh, Lq] fp32 = log sum_j exp(score_ij) over the visible keys
+ * (natural log, scores scaled by 64^-1/2), NULL = not written; ssak_dec_attention_fwd is this launch with lse = NULL, its ctx
+ * bit-identical.
+ *
+ * ssak_dec_attention_bwd.  q, k, v, klens / klens_host, causal, q_offset exactly as the forward took them; ctx and dctx
+ * [B * Lq, nh * 64] bf16, lse [B, nh, Lq] as the forward wrote it.  P_ij = exp(score_ij - lse_i) on the forward's visible keys, 0
+ * elsewhere; delta_i = sum_d dctx_i ctx_i (written to delta [B, nh, Lq] fp32, scratch the second kernel reads);
+ * dP = dctx v^T, dS = P (dP - delta), dq = 64^-1/2 dS k, dk = 64^-1/2 dS^T q, dv = P^T dctx.  P and dS enter their products
+ * rounded to bf16.  dq [B * Lq, lddq], dk [B * Lk, lddk], dv [B * Lk, lddv] bf16 with their own pointers and row strides
+ * (multiples of 8, >= nh * 64; 16-byte aligned): self-attention writes the three column blocks of one packed [B * L, 3 D] buffer,
+ * cross-attention dq and a [B * S, 2 D] dk|dv buffer.  Only columns [64 h, 64 h + 64) of each row are written; EVERY row is
+ * written, rows of dk / dv at keys >= klens[b] as zeros.  Lq != Lk is fine (Lq 1 .. 448, Lk 1 .. 1500 are the decoder's shapes).
+ *
+ * ssak_dec_ce_bwd.  Per row r of fp32 logits [R, ldv] (V valid columns) with targets (device) / targets_host (host, the same
+ * values; negative = HF's -100 = ignored; a target >= V is SSAK_ERR_INVALID): lse and logprob as ssak_token_logprobs defines
+ * them; dlogits [R, ldd] bf16 (ldd >= V) = (exp(x_c - lse) - [c == target]) * grad_scale on a scored row, 0 on an ignored row
+ * and in columns [V, ldd); row_loss [R] fp32 = -logprob (0 on an ignored row); loss_sum [1] += the sum of row_loss in a fixed
+ * order (the caller zeroes it and forms HF's mean over the scored tokens).  row_loss and loss_sum may be NULL (loss_sum needs
+ * row_loss): a backward whose loss the forward already has asks for dlogits alone, one launch.
+ *
+ * ssak_dec_embed_bwd.  dh [B * L, D] bf16, row b * L + i the gradient of ssak_dec_embed's out[b, i].  d_embed_tokens [Vp, D] fp32
+ * += the rows gathered per token; d_embed_positions [max_positions, D] fp32, row pos_offset + i += sum_b dh[b, i] in batch order.
+ * The gather is a CSR the caller builds from the ids it holds (ssak_amd.hip.dec_embed_csr): uniq [n_unique] the distinct ids
+ * ascending, offsets [n_unique + 1] from 0 to B * L, rows [B * L] the row indices of each id ascending; device and host copies
+ * of each.  One workgroup per unique id sums its rows in that order.  The host copies are validated (ids inside [0, Vp), every
+ * row exactly once).
+ *
+ * ssak_layernorm_fwd_stats / ssak_layernorm_bwd.  The templates behind ssak_debug_layernorm_fwd / _bwd without dropout sites:
+ * r = res + y -> r_out (may be NULL), out = LN(r) gamma + beta, mean / rstd [M] fp32 saved; backward: a = g1 + g2 (g2 may be
+ * NULL), dr = LN_bwd(a) + g_res (g_res may be NULL), dgamma / dbeta [C] += the column sums (two-stage, fixed order);
+ * workspace >= ssak_layernorm_bwd_workspace_bytes(C).  dtype 0 = bf16 / 1 = fp32; C a multiple of 8, <= 1536. */
+int ssak_dec_attention_fwd_lse(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, int Lk, const int32_t* klens,
+                               const int32_t* klens_host /*host*/, int B, int Lq, int nh, int head_dim, int causal, int q_offset, void* ctx,
+                               float* lse, void* stream);
+int ssak_dec_attention_bwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, int Lk, const int32_t* klens,
+                           const int32_t* klens_host /*host*/, int B, int Lq, int nh, int head_dim, int causal, int q_offset, const void* ctx,
+                           const float* lse, const void* dctx, void* dq, long lddq, void* dk, long lddk, void* dv, long lddv, float* delta,
+                           void* stream);
+int ssak_dec_ce_bwd(const float* logits, int R, int V, long ldv, const int32_t* targets, const int32_t* targets_host /*host*/, float grad_scale,
+                    void* dlogits, long ldd, float* row_loss, float* loss_sum, void* stream);
+int ssak_dec_embed_bwd(const void* dh, int B, int L, int D, int Vp, int max_positions, int pos_offset, const int32_t* uniq,
+                       const int32_t* offsets, const int32_t* rows, const int32_t* uniq_host /*host*/, const int32_t* offsets_host /*host*/,
+                       const int32_t* rows_host /*host*/, int n_unique, float* d_embed_tokens, float* d_embed_positions, void* stream);
+int ssak_layernorm_fwd_stats(const void* y, const void* res, const float* gamma, const float* beta, void* r_out, void* out, float* mean,
+                             float* rstd, int M, int C, float eps, int dtype, void* stream);
+size_t ssak_layernorm_bwd_workspace_bytes(int C);
+int ssak_layernorm_bwd(const void* g1, const void* g2, const void* r, const float* mean, const float* rstd, const float* gamma,
+                       const void* g_res, void* dr, float* dgamma, float* dbeta, int M, int C, int dtype, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* ---- TEST-ONLY entries (not part of the product path; kept in the release library so that the parity tests run against the
  * library that ships): dropout bits of one site ------------------------------------------------------------------------

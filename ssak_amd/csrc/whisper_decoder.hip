@@ -2,7 +2,8 @@
 // (causal self-attention over a packed q|k|v buffer, cross-attention over the encoder-side k|v buffer) and the per-row
 // log-softmax statistics of the vocabulary projection.  Everything else of a decoder layer is ssak_gemm_bf16 with its bias /
 // GELU epilogues and the residual + LayerNorm row kernel of norm_act.hip (ssak_layernorm_fwd); the sequencing is Python
-// (ssak_amd/whisper_seq2seq.py).  bf16 storage, fp32 accumulation.  There is no backward, so nothing is saved.
+// (ssak_amd/whisper_seq2seq.py).  bf16 storage, fp32 accumulation.  The backward is whisper_train.hip (ABI 650); what it reads of this
+// file's forward is the attention's log-sum-exp (ssak_dec_attention_fwd_lse).
 //
 // dec_attn_kernel.  One workgroup per (utterance, head, 16 queries), 16 being the M of v_mfma_f32_16x16x32_bf16; decoder
 // shapes are 1 .. 448 queries against up to 1500 keys, so the key range, not the query range, is what the four waves split:
@@ -49,12 +50,14 @@ constexpr int DA_THREADS = 64 * DA_WAVES;
 constexpr int DA_VP = DA_KT + 8;  // bf16 pitch of the V^T image: 80-byte rows keep the 16-byte reads aligned and off one bank group
 constexpr int DA_OP = DA_HD + 4;  // fp32 pitch of a wave's partial O
 constexpr float DA_LOG2E = 1.4426950408889634f;
+constexpr float DA_LN2 = 0.6931471805599453f;
 
 struct DaParams {
   const bf16* q;
   const bf16* k;
   const bf16* v;
   bf16* ctx;
+  float* lse;  // [B, nh, Lq] natural-log log-sum-exp of the scaled, masked scores, or null (ssak_dec_attention_fwd_lse)
   const int32_t* klens;
   long ldq, ldk, ldv;
   int Lq, Lk, nh, causal, q_offset;
@@ -207,6 +210,7 @@ __global__ __launch_bounds__(DA_THREADS) void dec_attn_kernel(const DaParams p) 
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = L > 0.f ? o[e] / L : 0.f;
       st8<bf16>(p.ctx + ((long)b * p.Lq + q0 + qq) * D + h * DA_HD + 8 * ch, f_to_chunk8<bf16>(o));
+      if (p.lse && ch == 0) p.lse[((long)b * p.nh + h) * p.Lq + q0 + qq] = (M + log2f(L)) * DA_LN2;
     }
   }
 }
@@ -337,9 +341,9 @@ extern "C" int ssak_dec_embed(const void* embed_tokens, const void* embed_positi
   return SSAK_OK;
 }
 
-extern "C" int ssak_dec_attention_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, int Lk, const int32_t* klens,
-                                      const int32_t* klens_host, int B, int Lq, int nh, int head_dim, int causal, int q_offset, void* ctx,
-                                      void* stream) {
+extern "C" int ssak_dec_attention_fwd_lse(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, int Lk, const int32_t* klens,
+                                          const int32_t* klens_host, int B, int Lq, int nh, int head_dim, int causal, int q_offset, void* ctx,
+                                          float* lse, void* stream) {
   SSAK_REQUIRE(q && k && v && ctx, "dec_attention_fwd: null pointer");
   SSAK_REQUIRE(head_dim == DA_HD, "dec_attention_fwd: head_dim=%d; the supported head dimension is %d", head_dim, DA_HD);
   SSAK_REQUIRE(B > 0 && B <= 65535 && Lq > 0 && Lk > 0 && nh > 0 && nh <= 65535, "dec_attention_fwd: bad shape B=%d Lq=%d Lk=%d nh=%d", B, Lq, Lk, nh);
@@ -354,12 +358,19 @@ extern "C" int ssak_dec_attention_fwd(const void* q, long ldq, const void* k, lo
     for (int b = 0; b < B; ++b)
       SSAK_REQUIRE(klens_host[b] >= 1 && klens_host[b] <= Lk, "dec_attention_fwd: klens[%d] = %d outside [1, %d]", b, klens_host[b], Lk);
   DaParams p;
-  p.q = (const bf16*)q, p.k = (const bf16*)k, p.v = (const bf16*)v, p.ctx = (bf16*)ctx, p.klens = klens;
+  p.q = (const bf16*)q, p.k = (const bf16*)k, p.v = (const bf16*)v, p.ctx = (bf16*)ctx, p.lse = lse, p.klens = klens;
   p.ldq = ldq, p.ldk = ldk, p.ldv = ldv;
   p.Lq = Lq, p.Lk = Lk, p.nh = nh, p.causal = causal != 0, p.q_offset = q_offset;
   dec_attn_kernel<<<dim3(ssak_cdiv(Lq, DA_QT), nh, B), DA_THREADS, 0, (hipStream_t)stream>>>(p);
   SSAK_LAUNCH_CHECK();
   return SSAK_OK;
+}
+
+// the same launch without the statistics
+extern "C" int ssak_dec_attention_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, int Lk, const int32_t* klens,
+                                      const int32_t* klens_host, int B, int Lq, int nh, int head_dim, int causal, int q_offset, void* ctx,
+                                      void* stream) {
+  return ssak_dec_attention_fwd_lse(q, ldq, k, ldk, v, ldv, Lk, klens, klens_host, B, Lq, nh, head_dim, causal, q_offset, ctx, nullptr, stream);
 }
 
 extern "C" int ssak_token_logprobs(const void* logits, int dtype, int R, int V, long ldv, const int32_t* targets, const int32_t* targets_host,

@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 640  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 650  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -193,6 +193,14 @@ def _load():
         "ssak_dec_attention_step_grouped": (i32, [vp, C.c_long, vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, i32, vp, i32, i32, i32, i32, i32, vp,
                                                   sz, vp, vp]),
         "ssak_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]),
+        "ssak_dec_attention_fwd_lse": (i32, [vp, C.c_long, vp, C.c_long, vp, C.c_long, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "ssak_dec_attention_bwd": (i32, [vp, C.c_long, vp, C.c_long, vp, C.c_long, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp,
+                                         C.c_long, vp, C.c_long, vp, C.c_long, vp, vp]),
+        "ssak_dec_ce_bwd": (i32, [vp, i32, i32, C.c_long, vp, vp, f32, vp, C.c_long, vp, vp, vp]),
+        "ssak_dec_embed_bwd": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
+        "ssak_layernorm_fwd_stats": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]),
+        "ssak_layernorm_bwd_workspace_bytes": (sz, [i32]),
+        "ssak_layernorm_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
         "ssak_debug_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, C.c_long, i32, vp, C.POINTER(f32), vp]),
         "ssak_debug_attention_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, i32, i32, i32, vp, vp]),
         "ssak_debug_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, C.c_uint64, C.c_uint32, f32, C.c_uint32,
@@ -950,6 +958,108 @@ def layernorm_fwd(y, res, gamma, beta, r_out=None, out=None, eps: float = 1e-5):
     M, Cc = x.shape
     check(lib.ssak_layernorm_fwd(ptr(y), ptr(res), ptr(gamma), ptr(beta), ptr(r_out), ptr(out), M, Cc, float(eps), _row_dtype(x), stream()))
     return out if out is not None else r_out
+
+
+# ------------------------------------------------------------------ Whisper training (ABI 650): the decoder's backward kernels
+def dec_attention_fwd_lse(q, k, v, B: int, Lq: int, Lk: int, nh: int, *, klens=None, causal: bool = False, q_offset: int = 0,
+                          head_dim: int = DEC_HEAD_DIM, ctx=None, lse=None):
+    """``ssak_dec_attention_fwd_lse``: :func:`dec_attention_fwd` that also writes lse [B, nh, Lq] fp32, the natural-log
+    log-sum-exp of each query's scaled, masked scores (what :func:`dec_attention_bwd` recomputes P from) -> (ctx, lse)."""
+    for t in (q, k, v):
+        assert t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1
+    assert q.shape[0] == B * Lq and k.shape[0] == B * Lk and v.shape[0] == B * Lk, "q holds B * Lq rows, k and v B * Lk"
+    kl_h = None if klens is None else _host_i32(klens, B, "klens")
+    kl_d = None if kl_h is None else torch.from_numpy(kl_h).to(q.device)
+    ctx = torch.empty((B * Lq, nh * head_dim), dtype=torch.bfloat16, device=q.device) if ctx is None else ctx
+    assert ctx.dtype == torch.bfloat16 and ctx.is_contiguous() and ctx.shape == (B * Lq, nh * head_dim)
+    lse = torch.empty((B, nh, Lq), dtype=torch.float32, device=q.device) if lse is None else lse
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() == B * nh * Lq
+    check(lib.ssak_dec_attention_fwd_lse(ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), int(Lk), ptr(kl_d), _hp(kl_h), B,
+                                         int(Lq), int(nh), int(head_dim), int(bool(causal)), int(q_offset), ptr(ctx), ptr(lse), stream()))
+    return ctx, lse
+
+
+def dec_attention_bwd(q, k, v, ctx, lse, dctx, dq, dk, dv, B: int, Lq: int, Lk: int, nh: int, *, klens=None, causal: bool = False,
+                      q_offset: int = 0, head_dim: int = DEC_HEAD_DIM, delta=None):
+    """``ssak_dec_attention_bwd``: q, k, v and the mask as the forward took them, ctx / lse as it wrote them, dctx [B * Lq, nh * 64]
+    -> dq [B * Lq, .], dk / dv [B * Lk, .] bf16 written into the caller's 2-D tensors or column slices (their row strides are
+    passed on; rows of dk / dv at keys >= klens[b] are written as zeros).  Returns delta [B, nh, Lq] fp32."""
+    for t in (q, k, v, dq, dk, dv):
+        assert t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1
+    for t in (ctx, dctx):
+        assert t.dtype == torch.bfloat16 and t.is_contiguous() and t.shape == (B * Lq, nh * head_dim)
+    assert q.shape[0] == B * Lq and k.shape[0] == B * Lk and v.shape[0] == B * Lk, "q holds B * Lq rows, k and v B * Lk"
+    assert dq.shape[0] == B * Lq and dk.shape[0] == B * Lk and dv.shape[0] == B * Lk
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() == B * nh * Lq
+    kl_h = None if klens is None else _host_i32(klens, B, "klens")
+    kl_d = None if kl_h is None else torch.from_numpy(kl_h).to(q.device)
+    delta = torch.empty((B, nh, Lq), dtype=torch.float32, device=q.device) if delta is None else delta
+    assert delta.dtype == torch.float32 and delta.is_contiguous() and delta.numel() == B * nh * Lq
+    check(lib.ssak_dec_attention_bwd(ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), int(Lk), ptr(kl_d), _hp(kl_h), B, int(Lq),
+                                     int(nh), int(head_dim), int(bool(causal)), int(q_offset), ptr(ctx), ptr(lse), ptr(dctx), ptr(dq),
+                                     dq.stride(0), ptr(dk), dk.stride(0), ptr(dv), dv.stride(0), ptr(delta), stream()))
+    return delta
+
+
+def dec_ce_bwd(logits: torch.Tensor, V: int, targets, grad_scale: float = 1.0, dlogits=None, loss_sum=None, want_loss: bool = True):
+    """``ssak_dec_ce_bwd`` on fp32 logits [R, ldv] (the first V columns valid) with host ``targets`` [R] (negative: ignored) ->
+    (dlogits [R, ldd] bf16, row_loss [R] fp32 = -logprob, loss_sum [1] fp32).  ``loss_sum`` is added to when given (zeros
+    otherwise); ``dlogits`` defaults to ldd = ldv.  ``want_loss=False``: dlogits alone, one launch -> (dlogits, None, None)."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    R, dev = logits.shape[0], logits.device
+    tg_h = _host_i32(targets, R, "targets")
+    tg_d = torch.from_numpy(tg_h).to(dev)
+    dlogits = torch.empty((R, logits.shape[1]), dtype=torch.bfloat16, device=dev) if dlogits is None else dlogits
+    assert dlogits.dtype == torch.bfloat16 and dlogits.dim() == 2 and dlogits.stride(1) == 1 and dlogits.shape[0] == R
+    row_loss = torch.empty(R, dtype=torch.float32, device=dev) if want_loss else None
+    loss_sum = None if not want_loss else torch.zeros(1, dtype=torch.float32, device=dev) if loss_sum is None else loss_sum
+    check(lib.ssak_dec_ce_bwd(ptr(logits), R, int(V), logits.stride(0), ptr(tg_d), _hp(tg_h), float(grad_scale), ptr(dlogits),
+                              dlogits.stride(0), ptr(row_loss), ptr(loss_sum), stream()))
+    return dlogits, row_loss, loss_sum
+
+
+def dec_embed_csr(ids):
+    """ids [B, L] (or flat) -> (uniq, offsets, rows) int32: the distinct ids ascending, and for each the indices of the rows that
+    hold it, ascending, as one CSR -- the fixed summation order of :func:`dec_embed_bwd`."""
+    flat = np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
+    order = np.argsort(flat, kind="stable")  # stable: equal ids keep their rows ascending
+    uniq, counts = np.unique(flat, return_counts=True)
+    offsets = np.concatenate([[0], np.cumsum(counts)])
+    return uniq.astype(np.int32), offsets.astype(np.int32), order.astype(np.int32)
+
+
+def dec_embed_bwd(dh: torch.Tensor, ids, d_embed_tokens: torch.Tensor, d_embed_positions: torch.Tensor, pos_offset: int = 0):
+    """``ssak_dec_embed_bwd``: dh [B * L, D] bf16 and the host ``ids`` [B, L] of the forward -> d_embed_tokens [Vp, D] fp32 += the
+    rows of each token (fixed order: :func:`dec_embed_csr`), d_embed_positions [max_pos, D] fp32 += the sums over the batch."""
+    ids_np = ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)
+    B, L = ids_np.shape
+    D = dh.shape[1]
+    assert dh.is_cuda and dh.dtype == torch.bfloat16 and dh.is_contiguous() and dh.shape[0] == B * L
+    for t in (d_embed_tokens, d_embed_positions):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[1] == D
+    host = [np.ascontiguousarray(a) for a in dec_embed_csr(ids_np)]
+    dev = [torch.from_numpy(a).to(dh.device) for a in host]
+    check(lib.ssak_dec_embed_bwd(ptr(dh), B, L, D, d_embed_tokens.shape[0], d_embed_positions.shape[0], int(pos_offset), ptr(dev[0]),
+                                 ptr(dev[1]), ptr(dev[2]), _hp(host[0]), _hp(host[1]), _hp(host[2]), host[0].shape[0], ptr(d_embed_tokens),
+                                 ptr(d_embed_positions), stream()))
+
+
+def layernorm_fwd_stats(y, res, gamma, beta, out, mean, rstd, r_out=None, eps: float = 1e-5):
+    """``ssak_layernorm_fwd_stats``: :func:`layernorm_fwd` that saves mean / rstd [M] fp32 for :func:`layernorm_bwd`."""
+    x = y if y is not None else res
+    M, Cc = x.shape
+    check(lib.ssak_layernorm_fwd_stats(ptr(y), ptr(res), ptr(gamma), ptr(beta), ptr(r_out), ptr(out), ptr(mean), ptr(rstd), M, Cc, float(eps),
+                                       _row_dtype(x), stream()))
+    return out
+
+
+def layernorm_bwd(g1, g2, r, mean, rstd, gamma, g_res, dr, dgamma, dbeta, workspace=None):
+    """``ssak_layernorm_bwd``: dr = LN_bwd(g1 + g2) + g_res (g2, g_res may be None); dgamma / dbeta [C] fp32 += the column sums."""
+    M, Cc = r.shape
+    ws = workspace if workspace is not None else _ws(lib.ssak_layernorm_bwd_workspace_bytes(Cc), r.device)
+    check(lib.ssak_layernorm_bwd(ptr(g1), ptr(g2), ptr(r), ptr(mean), ptr(rstd), ptr(gamma), ptr(g_res), ptr(dr), ptr(dgamma), ptr(dbeta), M, Cc,
+                                 _row_dtype(r), ptr(ws), ws.numel(), stream()))
+    return dr
 
 
 # ------------------------------------------------------------------ test-only: the dropout bits of one site

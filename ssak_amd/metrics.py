@@ -50,3 +50,19 @@ def compute_metrics(logits: torch.Tensor, labels: torch.Tensor, vocab: Sequence[
     acc = WerAccumulator(vocab, pad_id, logits.device)
     acc.add(logits, labels, frame_lens)
     return acc.compute()
+
+
+def text_wer(references: Sequence[str], hypotheses: Sequence[str]) -> dict:
+    """Word error rate of decoded transcripts (the seq2seq models' validation: the hypotheses come from ``generate``, not from
+    frame logits): Levenshtein distance over whitespace-separated words, summed over the utterances -> {"wer", "edits", "ref_words"}."""
+    edits = words = 0
+    for ref, hyp in zip(references, hypotheses):
+        r, h = ref.split(), hyp.split()
+        row = list(range(len(h) + 1))
+        for i, rw in enumerate(r, 1):
+            prev, row[0] = row[0], i
+            for j, hw in enumerate(h, 1):
+                prev, row[j] = row[j], min(row[j] + 1, row[j - 1] + 1, prev + (rw != hw))
+        edits += row[len(h)]
+        words += len(r)
+    return {"wer": edits / max(words, 1), "edits": edits, "ref_words": words}

@@ -39,7 +39,8 @@ best_of=N, seed=s)``): ``ssak_dec_sample_step`` draws each token from the filter
 the host; the temperature fallback on ``compression_ratio_threshold`` / ``logprob_threshold`` is the host loop of
 ssak_amd/whisper_transcribe.py (DESIGN.md "Whisper sampling and temperature fallback").  Not built: a beam ``patience``,
 ``condition_on_previous_text`` / ``initial_prompt``, word timestamps, a skinny-M GEMM for the token step, hipGraph capture
-of the step, training / LoRA, an fp32-exact mode of the decoder.  Timing: tools/bench_whisper_decoder.py,
+of the step, LoRA, an fp32-exact mode of the decoder.  Full fine-tuning (``forward_train`` / ``backward``, ``python -m
+ssak_amd.train_whisper``) is ssak_amd/whisper_train.py (DESIGN.md "Whisper fine-tuning").  Timing: tools/bench_whisper_decoder.py,
 tools/bench_whisper_generate.py, tools/bench_whisper_transcribe.py, tools/bench_whisper_beam.py, tools/bench_whisper_sample.py
 (DESIGN.md "Whisper decoder", "Whisper generation", "Whisper long-form transcription", "Whisper beam search", "Whisper sampling and
 temperature fallback").
@@ -57,6 +58,7 @@ import torch
 
 from . import hip
 from .whisper import WhisperCTCConfig, WhisperEncoderForCTC
+from .whisper_train import WhisperTrainMixin
 
 ROW_CHUNK = 256  # rows of the vocabulary projection in flight (51 865 columns: 53 MB of fp32 logits)
 N_SAMPLES = 480000  # Whisper's 30 s window at 16 kHz
@@ -93,6 +95,12 @@ class WhisperSeq2SeqConfig:
     # <|nospeech|> token (None: no_timestamps_token_id - 1, where Whisper's vocabularies have it)
     max_initial_timestamp_index: Optional[int] = 50
     no_speech_token_id: Optional[int] = None
+    # the regularisers of config.json: inference ignores them, forward_train() refuses any that is > 0
+    dropout: float = 0.0
+    attention_dropout: float = 0.0
+    activation_dropout: float = 0.0
+    decoder_layerdrop: float = 0.0
+    encoder_layerdrop: float = 0.0
 
     def __post_init__(self):
         for what, heads in (("encoder", self.encoder_attention_heads), ("decoder", self.decoder_attention_heads)):
@@ -274,10 +282,12 @@ def _decoder_layout(cfg: WhisperSeq2SeqConfig):
     return layout, off
 
 
-class WhisperSeq2Seq:
+class WhisperSeq2Seq(WhisperTrainMixin):
     """``WhisperSeq2Seq.from_pretrained(folder)``; :meth:`encode`, :meth:`decode_logprobs`, :meth:`score`, :meth:`detect_language`,
-    :meth:`generate`, :meth:`transcribe`.  Two layer walks (:meth:`_decoder_hidden`, teacher-forced; :meth:`_gen_step`, one row on the
-    cache), one chunked vocabulary projection (:meth:`_project_chunks`) and one generation loop (:meth:`_gen_loop`)."""
+    :meth:`generate`, :meth:`transcribe`; training: :meth:`forward_train`, :meth:`backward`, :meth:`save_pretrained`
+    (ssak_amd/whisper_train.py).  Two layer walks (:meth:`_decoder_hidden`, teacher-forced; :meth:`_gen_step`, one row on the
+    cache; the training walk of ssak_amd/whisper_train.py is the teacher-forced one with everything kept that the backward reads), one
+    chunked vocabulary projection (:meth:`_project_chunks`) and one generation loop (:meth:`_gen_loop`)."""
 
     def __init__(self, config: WhisperSeq2SeqConfig, device: str = "cuda:0", seed: int = 69):
         if not torch.cuda.is_available():
@@ -336,7 +346,7 @@ class WhisperSeq2Seq:
         return self
 
     @classmethod
-    def from_pretrained(cls, folder: str, device: str = "cuda:0") -> "WhisperSeq2Seq":
+    def from_pretrained(cls, folder: str, device: str = "cuda:0", freeze_encoder: bool = False) -> "WhisperSeq2Seq":
         """An HF ``WhisperForConditionalGeneration`` folder: ``config.json``, ``model.safetensors`` / ``pytorch_model.bin``,
         ``generation_config.json`` for ``lang_to_id`` and ``decoder_start_token_id`` (else the ``<|xx|>`` entries of
         ``added_tokens.json`` / ``vocab.json``) and for what :meth:`generate` needs: ``eos_token_id``, ``pad_token_id``,
@@ -381,6 +391,7 @@ class WhisperSeq2Seq:
         model.encoder.load_state_dict({k: v for k, v in enc.items() if k in model.encoder.layout}, strict=False)
         model.load_decoder_state_dict(sd)
         model.name_or_path = folder
+        model.freeze_encoder = bool(freeze_encoder)  # (training only: forward_train / backward / WhisperAdamW leave the encoder alone)
         return model
 
     # ------------------------------------------------------------------ encoder
