@@ -739,18 +739,30 @@ def dec_embed(embed_tokens: torch.Tensor, embed_positions: torch.Tensor, ids, po
     return out
 
 
+def _dec_attention_fwd(q, k, v, B, Lq, Lk, nh, klens, causal, q_offset, head_dim, ctx, lse):
+    """:func:`dec_attention_fwd` (``lse`` None) and :func:`dec_attention_fwd_lse`: one body, the entry with or without the lse output."""
+    for t in (q, k, v):
+        assert t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1
+    assert q.shape[0] == B * Lq and k.shape[0] == B * Lk and v.shape[0] == B * Lk, "q holds B * Lq rows, k and v B * Lk"
+    kl_h = None if klens is None else _host_i32(klens, B, "klens")
+    kl_d = None if kl_h is None else torch.from_numpy(kl_h).to(q.device)
+    ctx = torch.empty((B * Lq, nh * head_dim), dtype=torch.bfloat16, device=q.device) if ctx is None else ctx
+    assert ctx.dtype == torch.bfloat16 and ctx.is_contiguous() and ctx.shape == (B * Lq, nh * head_dim)
+    args = (ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), int(Lk), ptr(kl_d), _hp(kl_h), B, int(Lq), int(nh), int(head_dim),
+            int(bool(causal)), int(q_offset), ptr(ctx))
+    if lse is None:
+        check(lib.ssak_dec_attention_fwd(*args, stream()))
+    else:
+        assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() == B * nh * Lq
+        check(lib.ssak_dec_attention_fwd_lse(*args, ptr(lse), stream()))
+    return ctx, lse
+
+
 def dec_attention_fwd(q, k, v, B: int, Lq: int, Lk: int, nh: int, *, klens=None, causal: bool = False, q_offset: int = 0,
                       head_dim: int = DEC_HEAD_DIM, ctx=None):
     """``ssak_dec_attention_fwd``: q [B * Lq, ldq], k / v [B * Lk, ldk / ldv] bf16 -- 2-D tensors or column slices of one (their row
     stride is passed on) -> ctx [B * Lq, nh * 64] bf16.  ``klens``: host values [B] (None: all Lk keys)."""
-    for t in (q, k, v):
-        assert t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1
-    kl_h = None if klens is None else _host_i32(klens, B, "klens")
-    kl_d = None if kl_h is None else torch.from_numpy(kl_h).to(q.device)
-    ctx = torch.empty((B * Lq, nh * head_dim), dtype=torch.bfloat16, device=q.device) if ctx is None else ctx
-    check(lib.ssak_dec_attention_fwd(ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), int(Lk), ptr(kl_d), _hp(kl_h), B, int(Lq),
-                                     int(nh), int(head_dim), int(bool(causal)), int(q_offset), ptr(ctx), stream()))
-    return ctx
+    return _dec_attention_fwd(q, k, v, B, Lq, Lk, nh, klens, causal, q_offset, head_dim, ctx, None)[0]
 
 
 def token_logprobs(logits: torch.Tensor, V: int, targets=None, allowed=None):
@@ -779,22 +791,11 @@ def dec_attention_step_workspace(B: int, nh: int, n_split: int = 0, device="cuda
 
 
 def dec_attention_step(q, k, v, n_keys: int, nh: int, *, klens=None, n_split: int = 0, workspace=None, head_dim: int = DEC_HEAD_DIM, ctx=None):
-    """``ssak_dec_attention_step``: q [B, ldq]; k / v [B, capacity, ld] bf16 views (row and per-utterance strides are passed on: a
-    cache with spare capacity, column slices of a packed k|v buffer) -> ctx [B, nh * 64] bf16 over the keys ``< n_keys`` and
-    ``< klens[b]``.  ``klens``: an int32 DEVICE tensor [B] the caller has validated (>= 1), or None.  ``n_split``: 0 = the library
+    """:func:`dec_attention_step_grouped` with ``group = 1`` (all ``ssak_dec_attention_step`` does): q [B, ldq]; k / v [B, capacity,
+    ld] bf16 views (row and per-utterance strides are passed on: a cache with spare capacity, column slices of a packed k|v
+    buffer) -> ctx [B, nh * 64] bf16 over the keys ``< n_keys`` and ``< klens[b]``.  ``klens``: an int32 DEVICE tensor [B] the caller has validated (>= 1), or None.  ``n_split``: 0 = the library
     chooses.  ``workspace``: from :func:`dec_attention_step_workspace` (allocated per call when None)."""
-    assert q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 2 and q.stride(1) == 1
-    for t in (k, v):
-        assert t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 3 and t.stride(2) == 1 and t.shape[0] == q.shape[0]
-    assert klens is None or (klens.is_cuda and klens.dtype == torch.int32 and klens.is_contiguous() and klens.numel() == q.shape[0])
-    B = q.shape[0]
-    if workspace is None:
-        workspace = dec_attention_step_workspace(B, nh, n_split, q.device)
-    ctx = torch.empty((B, nh * head_dim), dtype=torch.bfloat16, device=q.device) if ctx is None else ctx
-    check(lib.ssak_dec_attention_step(ptr(q), q.stride(0), ptr(k), k.stride(1), k.stride(0), ptr(v), v.stride(1), v.stride(0), int(n_keys),
-                                      ptr(klens), B, int(nh), int(head_dim), int(n_split), ptr(workspace), workspace.numel() * 4, ptr(ctx),
-                                      stream()))
-    return ctx
+    return dec_attention_step_grouped(q, k, v, n_keys, nh, 1, klens=klens, n_split=n_split, workspace=workspace, head_dim=head_dim, ctx=ctx)
 
 
 def _assert_masks(V: int, *masks):
@@ -812,10 +813,11 @@ def _h_next_dims(embed_tokens, embed_positions, h_next, rows: int):
     return D, max_pos
 
 
-def _token_step_args(logits, V, finished, n_unfinished, tokens, logprobs, t, eos_id, pad_id, suppress, begin_suppress, first, embed_tokens,
-                     embed_positions, next_pos, h_next):
-    """What :func:`dec_greedy_step` and :func:`dec_timestamp_step` check and pass alike -> the entries' leading arguments (logits ..
-    first) and the run from the embedding tables to ``t``."""
+def _token_step(entry, rules, tail, logits, V, finished, n_unfinished, tokens, logprobs, t, eos_id, pad_id, suppress, begin_suppress, first,
+                embed_tokens, embed_positions, next_pos, h_next):
+    """The one body of :func:`dec_greedy_step`, :func:`dec_timestamp_step` and :func:`dec_sample_step`: the checks, then ``entry`` with
+    the arguments the three share, the timestamp ``rules`` (ts_begin, no_timestamps_id, max_initial, ts_last; None for the entry
+    without them) and the entry's own ``tail``."""
     assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
     B = logits.shape[0]
     assert tokens.dtype == torch.int32 and logprobs.dtype == torch.float32 and tokens.shape == logprobs.shape and tokens.shape[0] == B
@@ -823,9 +825,15 @@ def _token_step_args(logits, V, finished, n_unfinished, tokens, logprobs, t, eos
     assert finished.dtype == torch.uint8 and finished.numel() == B and n_unfinished.dtype == torch.int32
     _assert_masks(V, suppress, begin_suppress)
     D, max_pos = _h_next_dims(embed_tokens, embed_positions, h_next, B)
-    return ((ptr(logits), logits.stride(0), B, int(V), ptr(suppress), ptr(begin_suppress), int(bool(first))),
-            (ptr(embed_tokens), ptr(embed_positions), D, max_pos, int(next_pos), int(eos_id), int(pad_id), ptr(finished), ptr(n_unfinished),
-             ptr(tokens), ptr(logprobs), tokens.shape[1], int(t)))
+    head = (ptr(logits), logits.stride(0), B, int(V), ptr(suppress), ptr(begin_suppress), int(bool(first)))
+    mid = (ptr(embed_tokens), ptr(embed_positions), D, max_pos, int(next_pos), int(eos_id), int(pad_id), ptr(finished), ptr(n_unfinished),
+           ptr(tokens), ptr(logprobs), tokens.shape[1], int(t))
+    if rules is not None:
+        ts_begin, no_timestamps_id, max_initial, ts_last = rules
+        assert ts_last is None or (ts_last.is_cuda and ts_last.dtype == torch.int32 and ts_last.numel() == B and ts_last.is_contiguous())
+        head += (int(ts_begin), int(no_timestamps_id), int(max_initial))
+        mid += (ptr(ts_last),)
+    check(entry(*head, *mid, ptr(h_next), *tail, stream()))
 
 
 def dec_greedy_step(logits, V: int, *, finished, n_unfinished, tokens, logprobs, t: int, eos_id: int, pad_id: int, suppress=None,
@@ -834,9 +842,8 @@ def dec_greedy_step(logits, V: int, *, finished, n_unfinished, tokens, logprobs,
     shape), ``finished`` (uint8 [B], read and written), ``n_unfinished`` (int32 [1]) and, when ``h_next`` [B, D] bf16 is given,
     the next step's input row ``embed_tokens[token] + embed_positions[next_pos]``.  ``suppress`` / ``begin_suppress``: uint8 [V]
     device masks.  Everything stays on the device."""
-    head, mid = _token_step_args(logits, V, finished, n_unfinished, tokens, logprobs, t, eos_id, pad_id, suppress, begin_suppress, first,
-                                 embed_tokens, embed_positions, next_pos, h_next)
-    check(lib.ssak_dec_greedy_step(*head, *mid, ptr(h_next), stream()))
+    _token_step(lib.ssak_dec_greedy_step, None, (), logits, V, finished, n_unfinished, tokens, logprobs, t, eos_id, pad_id, suppress,
+                begin_suppress, first, embed_tokens, embed_positions, next_pos, h_next)
 
 
 def dec_timestamp_step(logits, V: int, *, finished, n_unfinished, tokens, logprobs, t: int, eos_id: int, pad_id: int, ts_begin: int,
@@ -845,10 +852,8 @@ def dec_timestamp_step(logits, V: int, *, finished, n_unfinished, tokens, logpro
     """``ssak_dec_timestamp_step`` (ABI 620): :func:`dec_greedy_step` under whisper's timestamp rules.  ``ts_last``: int32 [B] on the
     device, the row's most recent timestamp id or -1 (written at ``t == 0``, read and updated afterwards); ``max_initial``: the
     largest index of the first timestamp, -1 for none.  The history is what the kernel wrote at ``tokens[:, :t]``."""
-    head, mid = _token_step_args(logits, V, finished, n_unfinished, tokens, logprobs, t, eos_id, pad_id, suppress, begin_suppress, first,
-                                 embed_tokens, embed_positions, next_pos, h_next)
-    assert ts_last is None or (ts_last.is_cuda and ts_last.dtype == torch.int32 and ts_last.numel() == logits.shape[0] and ts_last.is_contiguous())
-    check(lib.ssak_dec_timestamp_step(*head, int(ts_begin), int(no_timestamps_id), int(max_initial), *mid, ptr(ts_last), ptr(h_next), stream()))
+    _token_step(lib.ssak_dec_timestamp_step, (ts_begin, no_timestamps_id, max_initial, ts_last), (), logits, V, finished, n_unfinished, tokens,
+                logprobs, t, eos_id, pad_id, suppress, begin_suppress, first, embed_tokens, embed_positions, next_pos, h_next)
 
 
 def dec_sample_step(logits, V: int, *, finished, n_unfinished, tokens, logprobs, t: int, eos_id: int, pad_id: int, temperature: float, seed: int,
@@ -857,11 +862,9 @@ def dec_sample_step(logits, V: int, *, finished, n_unfinished, tokens, logprobs,
     """``ssak_dec_sample_step`` (ABI 640): :func:`dec_timestamp_step` (``ts_last=None``: :func:`dec_greedy_step`, no rules) drawing the
     token from ``softmax(x / temperature)`` over the filtered row instead of taking its maximum; the log-probability is the drawn
     token's under the untempered row.  The draw is a function of ``(seed, t, row, column)``: the same call gives the same bits."""
-    head, mid = _token_step_args(logits, V, finished, n_unfinished, tokens, logprobs, t, eos_id, pad_id, suppress, begin_suppress, first,
-                                 embed_tokens, embed_positions, next_pos, h_next)
-    assert ts_last is None or (ts_last.is_cuda and ts_last.dtype == torch.int32 and ts_last.numel() == logits.shape[0] and ts_last.is_contiguous())
-    check(lib.ssak_dec_sample_step(*head, int(ts_begin), int(no_timestamps_id), int(max_initial), *mid, ptr(ts_last), ptr(h_next),
-                                   float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, stream()))
+    _token_step(lib.ssak_dec_sample_step, (ts_begin, no_timestamps_id, max_initial, ts_last), (float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF),
+                logits, V, finished, n_unfinished, tokens, logprobs, t, eos_id, pad_id, suppress, begin_suppress, first, embed_tokens,
+                embed_positions, next_pos, h_next)
 
 
 # ------------------------------------------------------------------ Whisper beam search (ABI 630): nb hypotheses per audio, R = B * nb rows
@@ -965,18 +968,8 @@ def dec_attention_fwd_lse(q, k, v, B: int, Lq: int, Lk: int, nh: int, *, klens=N
                           head_dim: int = DEC_HEAD_DIM, ctx=None, lse=None):
     """``ssak_dec_attention_fwd_lse``: :func:`dec_attention_fwd` that also writes lse [B, nh, Lq] fp32, the natural-log
     log-sum-exp of each query's scaled, masked scores (what :func:`dec_attention_bwd` recomputes P from) -> (ctx, lse)."""
-    for t in (q, k, v):
-        assert t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1
-    assert q.shape[0] == B * Lq and k.shape[0] == B * Lk and v.shape[0] == B * Lk, "q holds B * Lq rows, k and v B * Lk"
-    kl_h = None if klens is None else _host_i32(klens, B, "klens")
-    kl_d = None if kl_h is None else torch.from_numpy(kl_h).to(q.device)
-    ctx = torch.empty((B * Lq, nh * head_dim), dtype=torch.bfloat16, device=q.device) if ctx is None else ctx
-    assert ctx.dtype == torch.bfloat16 and ctx.is_contiguous() and ctx.shape == (B * Lq, nh * head_dim)
     lse = torch.empty((B, nh, Lq), dtype=torch.float32, device=q.device) if lse is None else lse
-    assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() == B * nh * Lq
-    check(lib.ssak_dec_attention_fwd_lse(ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), int(Lk), ptr(kl_d), _hp(kl_h), B,
-                                         int(Lq), int(nh), int(head_dim), int(bool(causal)), int(q_offset), ptr(ctx), ptr(lse), stream()))
-    return ctx, lse
+    return _dec_attention_fwd(q, k, v, B, Lq, Lk, nh, klens, causal, q_offset, head_dim, ctx, lse)
 
 
 def dec_attention_bwd(q, k, v, ctx, lse, dctx, dq, dk, dv, B: int, Lq: int, Lk: int, nh: int, *, klens=None, causal: bool = False,

@@ -1,49 +1,43 @@
 """Whisper as the reference runs it -- encoder AND text decoder (``transformers.WhisperForConditionalGeneration``;
-ssak/infer/whisper_infer.py, ssak/train/transformers/whisper_train.py:432,498-507) -- as a teacher-forced pass, with the two uses
-that need no generation loop:
+ssak/infer/whisper_infer.py, ssak/train/transformers/whisper_train.py:432,498-507).
 
-* transcript scoring: the log-probability of every token of a GIVEN token sequence under the audio, their sum, Whisper's
-  ``avg_logprob`` (whisper/decoding.py: ``sum / (len + 1)``) and HF's seq2seq cross-entropy (the mean over labels other than
-  -100) -- what ``transcribe`` reports per segment and the forward half of the fine-tuning loss; data curation filters bad
-  transcripts with it;
-* language identification: openai-whisper's ``detect_language`` -- one decoder position after ``<|startoftranscript|>``, a
-  softmax restricted to the language tokens.
+What it is for: transcript scoring (:meth:`WhisperSeq2Seq.score`: every token's log-probability under the audio, their sum, Whisper's
+``avg_logprob`` and HF's cross-entropy; ``transcribe`` reports them per segment, data curation filters bad transcripts with them),
+language identification (:meth:`WhisperSeq2Seq.detect_language`, openai-whisper's: one decoder position, a softmax over the language
+tokens), generation (:meth:`WhisperSeq2Seq.generate`: greedy, beam search, sampling, each with or without timestamps;
+:meth:`WhisperSeq2Seq.transcribe`, ssak_amd/whisper_transcribe.py, seeks a 30 s window through files of any length by the timestamps
+it predicted and holds the temperature fallback) and full fine-tuning (ssak_amd/whisper_train.py).  Token ids are the contract: no
+tokenizer is shipped; :meth:`WhisperSeq2Seq.score_text` imports ``transformers.WhisperTokenizer`` lazily.
 
-The encoder is the HIP engine of :mod:`ssak_amd.whisper` (``arch = 1``) stopped at its hidden state, its CTC head left at zero
-and never run.  The decoder is Python sequencing over C entries, the way :mod:`ssak_amd.classify` composes its head:
-``ssak_dec_embed``, ``ssak_dec_attention_fwd`` (causal self-attention into the packed q|k|v buffer, cross-attention into the
-encoder-side k|v buffer), ``ssak_token_logprobs`` (ssak_amd/csrc/whisper_decoder.hip), ``ssak_gemm_bf16`` with its bias / GELU
-epilogues for every projection including the vocabulary projection against the tied embedding, and ``ssak_layernorm_fwd`` for
-the residual + LayerNorm between them.  Weights: fp32 masters with a bf16 shadow; activations bf16, logits fp32.  The logits of
-all ``B * L`` rows are never materialised at once: the vocabulary projection and the log-softmax run over chunks of
-``ROW_CHUNK`` rows, so the workspace is ``ROW_CHUNK * V * 4`` bytes whatever the batch.
+The encoder is the HIP engine of :mod:`ssak_amd.whisper` (``arch = 1``) stopped at its hidden state, its CTC head left at zero and
+never run.  The decoder is Python sequencing over C entries, the way :mod:`ssak_amd.classify` composes its head.  Weights: fp32
+masters with a bf16 shadow; activations bf16, logits fp32.  Its structure:
 
-Greedy generation (:meth:`WhisperSeq2Seq.generate`, what ssak/infer/whisper_infer.py asks of ``model.transcribe``: temperature 0, no
-beam, ``condition_on_previous_text = False``): every layer's cross k|v projection of the encoder output is computed once per
-call, the prompt is one teacher-forced pass whose self-attention k|v land in a cache, and each further token is one row per
-utterance through the layers -- ``ssak_dec_attention_step`` on the cache and on the cross buffer, ``ssak_dec_greedy_step`` for the
-logits processors, the arg-max, the log-probability, the finished flags and the next input row.  The loop stays on the device:
-the host reads one pinned word every ``poll_every`` steps and the tokens once at the end.
+* Two layer walks, and only these two spell a decoder layer (``ssak_gemm_bf16`` with bias / GELU epilogues for every product, q|k|v
+  and the cross k|v packed; ``ssak_layernorm_fwd`` for each residual + LayerNorm).  :meth:`WhisperSeq2Seq._decoder_hidden` is the
+  teacher-forced pass over [B, L] tokens (``ssak_dec_embed``, ``ssak_dec_attention_fwd``): scoring, language identification and the
+  prompt of a generation, whose self-attention k|v it leaves in the cache.  Training hooks in here: with ``keep`` the same pass calls
+  the entries that also write what the backward reads and keeps every buffer.  :meth:`WhisperSeq2Seq._gen_step` is one new row per
+  decoder row against the cache and the cross k|v buffer, in fixed buffers (``ssak_dec_attention_step``;
+  ``ssak_dec_attention_fwd`` at Lq = 1 on a cache shorter than ``STEP_SELF_MIN_KEYS``).
+* One chunked vocabulary projection against the tied embedding (:meth:`WhisperSeq2Seq._project_chunks`): the logits of all ``B * L``
+  rows never exist at once; the projection and what reads it (``ssak_token_logprobs``, the training loss and its backward) run over
+  ``row_chunk`` rows, so the workspace is ``row_chunk * V * 4`` bytes whatever the batch.
+* One generation loop (:meth:`WhisperSeq2Seq._gen_loop`: select, poll, step).  A call computes every layer's cross k|v projection of
+  the encoder output once (:meth:`WhisperSeq2Seq._gen_begin`), runs the prompt (:meth:`WhisperSeq2Seq._gen_prefill`) and stays on the
+  device: the host reads one pinned word every ``poll_every`` steps and the tokens once at the end.
+* The selections the loop is given.  The three token-step entries (``ssak_dec_greedy_step``; ``ssak_dec_timestamp_step``: whisper's
+  ``ApplyTimestampRules``; ``ssak_dec_sample_step``: a draw from the filtered distribution, ``best_of`` rows per utterance) launch one
+  kernel that applies the logits processors, picks the token, and writes its log-probability, the finished flags and the next input
+  row.  Beam search (:meth:`WhisperSeq2Seq._beam_step`: ``ssak_dec_beam_topk`` / ``ssak_dec_beam_select`` / ``ssak_dec_kv_reorder``)
+  keeps ``beam_size`` hypotheses per utterance on the device.  The host half is numpy: :func:`rows_finalize`, :func:`beam_finalize`,
+  :func:`beam_rank`.
 
-Greedy and beam search run the one loop :meth:`WhisperSeq2Seq._gen_loop` (select, poll the pinned word, step); they differ in the
-selection they pass it.  The two token-step entries launch one kernel, ``dec_token_step_kernel``, with and without the rules.
-
-With ``timestamps=True`` the step is ``ssak_dec_timestamp_step`` (whisper's ``ApplyTimestampRules`` on the device) and the call
-also returns ``no_speech_prob``; :meth:`WhisperSeq2Seq.transcribe` (ssak_amd/whisper_transcribe.py) seeks a 30 s window through
-files of any length by the timestamps it predicted, as ``model.transcribe`` does.
-
-Token ids are the contract (no tokenizer is needed, and none is shipped); :meth:`WhisperSeq2Seq.score_text` is a convenience
-that imports ``transformers.WhisperTokenizer`` lazily.  Beam search (``generate(beam_size=N)``, the reference's ``--beam_size`` / ``--accurate``): ``ssak_dec_beam_topk`` /
-``ssak_dec_beam_select`` / ``ssak_dec_kv_reorder`` keep N hypotheses per utterance on the device.  Sampling (``generate(temperature=T,
-best_of=N, seed=s)``): ``ssak_dec_sample_step`` draws each token from the filtered distribution, N candidates per utterance ranked on
-the host; the temperature fallback on ``compression_ratio_threshold`` / ``logprob_threshold`` is the host loop of
-ssak_amd/whisper_transcribe.py (DESIGN.md "Whisper sampling and temperature fallback").  Not built: a beam ``patience``,
-``condition_on_previous_text`` / ``initial_prompt``, word timestamps, a skinny-M GEMM for the token step, hipGraph capture
-of the step, LoRA, an fp32-exact mode of the decoder.  Full fine-tuning (``forward_train`` / ``backward``, ``python -m
-ssak_amd.train_whisper``) is ssak_amd/whisper_train.py (DESIGN.md "Whisper fine-tuning").  Timing: tools/bench_whisper_decoder.py,
-tools/bench_whisper_generate.py, tools/bench_whisper_transcribe.py, tools/bench_whisper_beam.py, tools/bench_whisper_sample.py
-(DESIGN.md "Whisper decoder", "Whisper generation", "Whisper long-form transcription", "Whisper beam search", "Whisper sampling and
-temperature fallback").
+Not built: a beam ``patience``, ``condition_on_previous_text`` / ``initial_prompt``, word timestamps, a skinny-M GEMM for the token
+step, hipGraph capture of the step, LoRA, an fp32-exact mode of the decoder.  Timing: tools/bench_whisper_decoder.py,
+tools/bench_whisper_generate.py, tools/bench_whisper_transcribe.py, tools/bench_whisper_beam.py, tools/bench_whisper_sample.py,
+tools/bench_whisper_train.py; DESIGN.md has a section for each ("Whisper decoder", "Whisper generation", "Whisper long-form
+transcription", "Whisper beam search", "Whisper sampling and temperature fallback", "Whisper fine-tuning").
 """
 from __future__ import annotations
 
@@ -227,6 +221,23 @@ class _BeamState:
     i: int = 0                            # steps taken = history entries per row
 
 
+@dataclasses.dataclass
+class _GenPlan:
+    """The arguments of :meth:`WhisperSeq2Seq.generate`, validated and normalised by :meth:`WhisperSeq2Seq._gen_plan`."""
+    prompt: Optional[np.ndarray]          # int64 [B, P]; None: the default prompt with the language this call detects
+    P: int                                # prompt width
+    n_max: int                            # token steps at most
+    eos: int
+    pad: int
+    sup: Optional[torch.Tensor]           # uint8 [V] device masks (:meth:`WhisperSeq2Seq._token_mask`)
+    bsup: Optional[torch.Tensor]
+    group: int                            # decoder rows per utterance: beam_size, or best_of, or 1
+    best_of: int                          # candidates drawn per utterance; 0: not sampling
+    ts: Optional[dict] = None             # timestamps: the rules' ts_begin, no_timestamps_id, max_initial
+    sot_row: Optional[int] = None         # timestamps: the prompt row no_speech_prob is read at, and its token
+    no_speech_id: Optional[int] = None
+
+
 def beam_finalize(tokens, sums, fin_tokens, fin_len, fin_sum, n_fin, steps: int, nb: int):
     """Host half of the beam search for one utterance: the finished sequences in the order they finished, then -- while fewer than
     ``nb`` -- the live hypotheses by ``list(np.argsort(sums))[::-1]`` (no eos, no eos term in their sum), skipping ``-inf`` ->
@@ -249,6 +260,44 @@ def beam_rank(cands, length_penalty=None) -> int:
         n = len(toks) - 1 if fin else len(toks)
         scores.append(-np.inf if n == 0 else s / (n if length_penalty is None else ((5 + n) / 6) ** length_penalty))
     return int(np.argmax(scores))
+
+
+def _rank_and_pack(cands, lps, pad: int, length_penalty=None) -> dict:
+    """Per utterance its candidates ``cands[b]`` ([(token list, sum, finished?, index)]) and their per-token log-probs ``lps[b]``:
+    :func:`beam_rank` picks one -> the :class:`GenerateResult` fields that describe the chosen ones, padded with ``pad`` / 0."""
+    picks = [beam_rank(c, length_penalty) for c in cands]
+    chosen = [c[w][0] for c, w in zip(cands, picks)]
+    lens = np.array([len(c) for c in chosen], dtype=np.int64)
+    n = int(lens.max())
+    tok, lp = np.full((len(cands), n), pad, dtype=np.int32), np.zeros((len(cands), n), dtype=np.float64)
+    for b, w in enumerate(picks):
+        tok[b, :lens[b]] = chosen[b]
+        lp[b, :lens[b]] = lps[b][w]
+    s = np.array([c[w][1] for c, w in zip(cands, picks)], dtype=np.float64)
+    return dict(tokens=chosen, lens=lens, token_array=tok, logprobs=lp, sum_logprob=s, avg_logprob=s / (lens + 1))
+
+
+def rows_finalize(tokens, logprobs, steps: int, eos: int, pad: int, best_of: int = 0, length_penalty=None) -> dict:
+    """Host half of greedy decoding and of sampling: ``tokens`` int32 / ``logprobs`` float64 [R, >= steps] as the loop wrote them
+    (a finished row goes on with ``pad`` and log-probability 0) -> the :class:`GenerateResult` fields other than ``steps`` and
+    ``no_speech_prob``.  A row ends with its first ``eos`` (``pad == eos`` or not), or after ``steps`` tokens.  ``best_of`` = 0:
+    greedy, one row per utterance.  ``best_of`` = n >= 1: n adjacent rows per utterance, ranked by :func:`beam_rank`, all of them
+    listed in ``samples`` / ``sample_logprobs`` in row order."""
+    tok, lp = tokens[:, :steps], logprobs[:, :steps]
+    lens = np.array([int(np.argmax(r == eos)) + 1 if (r == eos).any() else steps for r in tok], dtype=np.int64)
+    n = int(lens.max())
+    # a row's sum: sampling adds up the whole row, greedy its tokens in a row as long as the longest (the orders differ by a rounding)
+    sums = lp.sum(-1) if best_of else np.where(np.arange(n) < lens[:, None], lp[:, :n], 0.0).sum(-1)
+    group = max(best_of, 1)
+    cands, lps = [], []
+    for b in range(len(tok) // group):
+        rows = range(b * group, (b + 1) * group)
+        cands.append([(tok[r, :lens[r]].tolist(), float(sums[r]), bool((tok[r] == eos).any()), r) for r in rows])
+        lps.append([lp[r, :lens[r]].copy() for r in rows])
+    out = _rank_and_pack(cands, lps, pad, length_penalty)
+    if best_of:
+        out.update(samples=[[(c[0], c[1]) for c in cs] for cs in cands], sample_logprobs=lps)
+    return out
 
 
 def sample_call_seed(seed: int) -> int:
@@ -285,9 +334,7 @@ def _decoder_layout(cfg: WhisperSeq2SeqConfig):
 class WhisperSeq2Seq(WhisperTrainMixin):
     """``WhisperSeq2Seq.from_pretrained(folder)``; :meth:`encode`, :meth:`decode_logprobs`, :meth:`score`, :meth:`detect_language`,
     :meth:`generate`, :meth:`transcribe`; training: :meth:`forward_train`, :meth:`backward`, :meth:`save_pretrained`
-    (ssak_amd/whisper_train.py).  Two layer walks (:meth:`_decoder_hidden`, teacher-forced; :meth:`_gen_step`, one row on the
-    cache; the training walk of ssak_amd/whisper_train.py is the teacher-forced one with everything kept that the backward reads), one
-    chunked vocabulary projection (:meth:`_project_chunks`) and one generation loop (:meth:`_gen_loop`)."""
+    (ssak_amd/whisper_train.py).  The module docstring names the parts."""
 
     def __init__(self, config: WhisperSeq2SeqConfig, device: str = "cuda:0", seed: int = 69):
         if not torch.cuda.is_available():
@@ -422,52 +469,85 @@ class WhisperSeq2Seq(WhisperTrainMixin):
         raise ValueError(f"expected an encoder output [B, S, D] (bf16), input features [B, mels, frames] or waveforms [B, T]; got {tuple(x.shape)}")
 
     # ------------------------------------------------------------------ decoder
-    def _linear(self, x, w, bias, epilogue=hip.EPI_NONE):
+    def _linear(self, x, w, bias, epilogue=hip.EPI_NONE, out=None, **kw):
+        """An nn.Linear: x [M, K] against w [N, K] (+ bias, ``epilogue``) -> [M, N] bf16, fresh unless ``out`` is given."""
         M, K = x.shape
         N = w.shape[0]
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=self.device)
-        return hip.gemm(x, w, out, M, N, K, lda=K, ldb=K, ldc=N, bias=bias, epilogue=epilogue)
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=self.device) if out is None else out
+        return hip.gemm(x, w, out, M, N, K, lda=K, ldb=K, ldc=N, bias=bias, epilogue=epilogue, **kw)
 
-    def _decoder_hidden(self, enc: torch.Tensor, tokens: np.ndarray, enc_lens=None, pos_offset: int = 0, cross_kv=None,
-                        self_cache=None) -> torch.Tensor:
+    def _decoder_hidden(self, enc: torch.Tensor, tokens: np.ndarray, enc_lens=None, pos_offset: int = 0, cross_kv=None, self_cache=None,
+                        keep: Optional[list] = None):
         """The decoder stack on ``tokens`` [B, L] (teacher forcing) -> the final LayerNorm's output [B * L, D] bf16.  The prefill
         of :meth:`generate` passes ``cross_kv`` [layers, B * S, 2 D] (read instead of projecting the encoder output again) and
-        ``self_cache`` [layers, B, cap, 2 D] (receives each layer's self-attention k|v rows)."""
+        ``self_cache`` [layers, B, cap, 2 D] (receives each layer's self-attention k|v rows).
+
+        ``keep`` (a list, training): the same walk through the entries that also write what :meth:`backward` reads -- LayerNorm with
+        mean / rstd, attention with its log-sum-exp, fc1 with its pre-activation -- every buffer fresh; ``keep`` receives one dict
+        per layer (``ln1`` / ``ln2`` / ``ln3`` as (r, out, mean, rstd), ``qkv``, ``ctx_s``, ``lse_s``, ``q_c``, ``kv_c``, ``ctx_c``,
+        ``lse_c``, ``pre``, ``f``) and the final LayerNorm's tuple is returned in place of its output.  Without it nothing outlives
+        its layer: the residual stream alternates between two buffers and every LayerNorm writes the one ``x``."""
         cfg = self.config
         B, S, D = enc.shape
         if tokens.shape[0] != B:
             raise ValueError(f"{tokens.shape[0]} token sequences for {B} encoder outputs")
         L, nh = tokens.shape[1], cfg.decoder_attention_heads
         enc2 = enc.reshape(B * S, D)
+        bf = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=self.device)
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             h = hip.dec_embed(self._w("embed_tokens.weight"), self._w("embed_positions.weight"), tokens, pos_offset)
-            h2, x = torch.empty_like(h), torch.empty_like(h)
-            hip.layernorm_fwd(None, h, self._f("layers.0.self_attn_layer_norm.weight"), self._f("layers.0.self_attn_layer_norm.bias"), None, x)
+            x, spare = (bf(B * L, D), [bf(B * L, D)]) if keep is None else (None, None)
+
+            def norm(y, res, name):
+                """r = res + y (``res`` itself where ``y`` is None), LayerNorm ``name`` of it -> (r, out, mean, rstd)"""
+                g, b = self._f(name + ".weight"), self._f(name + ".bias")
+                if keep is not None:
+                    r, out, mean, rstd = res if y is None else bf(B * L, D), bf(B * L, D), f32(B * L), f32(B * L)
+                    hip.layernorm_fwd_stats(y, res, g, b, out, mean, rstd, r_out=None if y is None else r)
+                    return r, out, mean, rstd
+                r = res
+                if y is not None:
+                    r, spare[0] = spare[0], res
+                hip.layernorm_fwd(y, res, g, b, None if y is None else r, x)
+                return r, x, None, None
+
+            def attend(q, k, v, Lk, **mask):
+                """-> (ctx, lse | None)"""
+                if keep is not None:
+                    return hip.dec_attention_fwd_lse(q, k, v, B, L, Lk, nh, **mask)
+                return hip.dec_attention_fwd(q, k, v, B, L, Lk, nh, **mask), None
+
+            def fc1(x, p):
+                """GELU in fc1's epilogue -> (pre-activation | None, GELU of it)"""
+                pre = None if keep is None else bf(B * L, cfg.decoder_ffn_dim)
+                return pre, self._linear(x, self._w(p + "fc1.weight"), self._f(p + "fc1.bias"), hip.EPI_GELU, aux_out=pre)
+
+            ln = norm(None, h, "layers.0.self_attn_layer_norm")
             for l in range(cfg.decoder_layers):
                 p = f"layers.{l}."
+                s = {"ln1": ln}  # (the layer's buffers live in ``s`` alone: without ``keep`` they go when the next layer starts)
                 # causal self-attention: q | k | v in one product, the attention reads its three column blocks in place
-                qkv = self._linear(x, self._w(p + "self_attn.q_proj.weight", 3), self._f(p + "self_attn.q_proj.bias", 3))
+                s["qkv"] = self._linear(ln[1], self._w(p + "self_attn.q_proj.weight", 3), self._f(p + "self_attn.q_proj.bias", 3))
                 if self_cache is not None:
-                    self_cache[l, :, :L].copy_(qkv[:, D:].view(B, L, 2 * D))
-                ctx = hip.dec_attention_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, L, L, nh, causal=True, q_offset=0)
-                y = self._linear(ctx, self._w(p + "self_attn.out_proj.weight"), self._f(p + "self_attn.out_proj.bias"))
-                hip.layernorm_fwd(y, h, self._f(p + "encoder_attn_layer_norm.weight"), self._f(p + "encoder_attn_layer_norm.bias"), h2, x)
-                h, h2 = h2, h
+                    self_cache[l, :, :L].copy_(s["qkv"][:, D:].view(B, L, 2 * D))
+                s["ctx_s"], s["lse_s"] = attend(s["qkv"][:, :D], s["qkv"][:, D:2 * D], s["qkv"][:, 2 * D:], L, causal=True)
+                y = self._linear(s["ctx_s"], self._w(p + "self_attn.out_proj.weight"), self._f(p + "self_attn.out_proj.bias"))
+                s["ln2"] = ln = norm(y, ln[0], p + "encoder_attn_layer_norm")
                 # cross-attention: the layer's k | v projection of the encoder output, [B * S, 2 D]
-                q = self._linear(x, self._w(p + "encoder_attn.q_proj.weight"), self._f(p + "encoder_attn.q_proj.bias"))
-                kv = cross_kv[l] if cross_kv is not None else self._linear(enc2, self._w(p + "encoder_attn.k_proj.weight", 2),
-                                                                          self._f(p + "encoder_attn.k_proj.bias", 2))
-                ctx = hip.dec_attention_fwd(q, kv[:, :D], kv[:, D:], B, L, S, nh, klens=enc_lens)
-                y = self._linear(ctx, self._w(p + "encoder_attn.out_proj.weight"), self._f(p + "encoder_attn.out_proj.bias"))
-                hip.layernorm_fwd(y, h, self._f(p + "final_layer_norm.weight"), self._f(p + "final_layer_norm.bias"), h2, x)
-                h, h2 = h2, h
-                # feed-forward, GELU in fc1's epilogue
-                f = self._linear(x, self._w(p + "fc1.weight"), self._f(p + "fc1.bias"), hip.EPI_GELU)
-                y = self._linear(f, self._w(p + "fc2.weight"), self._f(p + "fc2.bias"))
-                nxt = f"layers.{l + 1}.self_attn_layer_norm." if l + 1 < cfg.decoder_layers else "layer_norm."
-                hip.layernorm_fwd(y, h, self._f(nxt + "weight"), self._f(nxt + "bias"), h2, x)
-                h, h2 = h2, h
-        return x
+                s["q_c"] = self._linear(ln[1], self._w(p + "encoder_attn.q_proj.weight"), self._f(p + "encoder_attn.q_proj.bias"))
+                s["kv_c"] = cross_kv[l] if cross_kv is not None else self._linear(enc2, self._w(p + "encoder_attn.k_proj.weight", 2),
+                                                                                  self._f(p + "encoder_attn.k_proj.bias", 2))
+                s["ctx_c"], s["lse_c"] = attend(s["q_c"], s["kv_c"][:, :D], s["kv_c"][:, D:], S, klens=enc_lens)
+                y = self._linear(s["ctx_c"], self._w(p + "encoder_attn.out_proj.weight"), self._f(p + "encoder_attn.out_proj.bias"))
+                s["ln3"] = ln = norm(y, ln[0], p + "final_layer_norm")
+                # feed-forward
+                s["pre"], s["f"] = fc1(ln[1], p)
+                y = self._linear(s["f"], self._w(p + "fc2.weight"), self._f(p + "fc2.bias"))
+                ln = norm(y, ln[0], f"layers.{l + 1}.self_attn_layer_norm" if l + 1 < cfg.decoder_layers else "layer_norm")
+                if keep is not None:
+                    keep.append(s)
+        return ln[1] if keep is None else ln
 
     def _project(self, x: torch.Tensor, n_rows: int) -> torch.Tensor:
         """Vocabulary projection of ``x`` [n, D] (n <= ``n_rows``, the chunk size the workspace is kept for) against the tied
@@ -492,11 +572,26 @@ class WhisperSeq2Seq(WhisperTrainMixin):
             yield r0, n, self._project(x[r0:r0 + n], chunk)
 
     @staticmethod
-    def _tokens(tokens, lens):
-        t = tokens.detach().cpu().numpy() if torch.is_tensor(tokens) else np.asarray(tokens)
-        if t.ndim != 2 or t.shape[1] < 1:
-            raise ValueError(f"tokens [B, L], got shape {t.shape}")
-        t = np.ascontiguousarray(t, dtype=np.int64)
+    def _ids(ids, what: str) -> np.ndarray:
+        """Token ids or labels [B, L], a tensor or host values -> a contiguous int64 host array."""
+        a = ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)
+        if a.ndim != 2 or a.shape[1] < 1:
+            raise ValueError(f"{what} [B, L], got shape {a.shape}")
+        return np.ascontiguousarray(a, dtype=np.int64)
+
+    @staticmethod
+    def _enc_lens(enc_lens, B: int, S: int) -> Optional[np.ndarray]:
+        """The encoder frames cross-attention may see, validated once -> int32 host values [B] (None: all S)."""
+        if enc_lens is None:
+            return None
+        lens = hip._host_i32(enc_lens, B, "enc_lens")
+        if lens.min() < 1 or lens.max() > S:
+            raise ValueError(f"enc_lens: {B} values in [1, {S}] expected, got {lens}")
+        return lens
+
+    @classmethod
+    def _tokens(cls, tokens, lens):
+        t = cls._ids(tokens, "tokens")
         B, L = t.shape
         lens = np.full(B, L, dtype=np.int64) if lens is None else np.asarray(lens.cpu() if torch.is_tensor(lens) else lens, dtype=np.int64)
         if lens.shape != (B,) or lens.min() < 1 or lens.max() > L:
@@ -596,12 +691,8 @@ class WhisperSeq2Seq(WhisperTrainMixin):
             raise ValueError("group > 1: the beams share the cross k|v buffer through the step kernel only (step_cross)")
         R = B * group
         cap = cfg.max_target_positions if cap is None else int(cap)
-        lens_host = lens_dev = None
-        if enc_lens is not None:
-            lens_host = hip._host_i32(enc_lens, B, "enc_lens")
-            if lens_host.min() < 1 or lens_host.max() > S:
-                raise ValueError(f"enc_lens: {B} values in [1, {S}] expected, got {lens_host}")
-            lens_dev = torch.from_numpy(lens_host).to(self.device)
+        lens_host = self._enc_lens(enc_lens, B, S)
+        lens_dev = None if lens_host is None else torch.from_numpy(lens_host).to(self.device)
         with torch.cuda.device(self.device):
             nl, nh = cfg.decoder_layers, cfg.decoder_attention_heads
             cross_kv = torch.empty((nl, B * S, 2 * D), dtype=torch.bfloat16, device=self.device)
@@ -644,12 +735,11 @@ class WhisperSeq2Seq(WhisperTrainMixin):
         """ctx [B, D] of the one new row: ``kv`` [B, rows, 2 D] is a layer's cache (``kind`` "self": the first ``n_keys`` rows
         are in use) or its cross k|v ("cross": all S rows, the encoder lengths on top)."""
         D, nh = st.D, self.config.decoder_attention_heads
-        if kind == "cross" and st.group > 1:  # the beams of an utterance read its one cross k|v
+        if kind == "cross" and st.step_cross:  # the rows of an utterance (beams, samples) read its one cross k|v
             return hip.dec_attention_step_grouped(q, kv[:, :, :D], kv[:, :, D:], n_keys, nh, st.group, klens=st.enc_lens, workspace=st.ws,
                                                   ctx=st.ctx)
-        if st.step_cross if kind == "cross" else (st.step_self_min_keys is not None and n_keys >= st.step_self_min_keys):
-            return hip.dec_attention_step(q, kv[:, :, :D], kv[:, :, D:], n_keys, nh, klens=st.enc_lens if kind == "cross" else None,
-                                          workspace=st.ws, ctx=st.ctx)
+        if kind == "self" and st.step_self_min_keys is not None and n_keys >= st.step_self_min_keys:
+            return hip.dec_attention_step(q, kv[:, :, :D], kv[:, :, D:], n_keys, nh, workspace=st.ws, ctx=st.ctx)
         rows = kv.shape[1]
         kv2 = kv.reshape(kv.shape[0] * rows, 2 * D)
         if kind == "self":  # the causal mask of a query at position n_keys - 1 hides the unused rows of the cache
@@ -660,10 +750,9 @@ class WhisperSeq2Seq(WhisperTrainMixin):
         """One token: ``h_in`` [B, D] bf16, the embedding row at position ``st.t`` (``ssak_dec_greedy_step``'s ``h_next``), through
         the layers against the cache and the cross buffer -> the logits [B, Vp] fp32 of that position.  Nothing is read back."""
         cfg = self.config
-        B, D, F, t = st.B * st.group, st.D, cfg.decoder_ffn_dim, st.t  # (B: the step's rows)
+        B, D, t = st.B * st.group, st.D, st.t  # (B: the step's rows)
         if t >= st.cap:
             raise ValueError(f"the cache of {st.cap} rows is full")
-        lin = lambda a, w, bias, out, N, K, epi=hip.EPI_NONE: hip.gemm(a, w, out, B, N, K, lda=K, ldb=K, ldc=N, bias=bias, epilogue=epi)
         with torch.cuda.device(self.device):
             h, h2, x = st.h, st.h2, st.x
             h.copy_(h_in)
@@ -671,20 +760,20 @@ class WhisperSeq2Seq(WhisperTrainMixin):
             for l in range(cfg.decoder_layers):
                 p = f"layers.{l}."
                 w3, b3 = self._w(p + "self_attn.q_proj.weight", 3), self._f(p + "self_attn.q_proj.bias", 3)
-                lin(x, w3[:D], b3[:D], st.q, D, D)
+                self._linear(x, w3[:D], b3[:D], out=st.q)
                 # the new row's k | v straight into row t of the layer's cache: C's row stride is one utterance's cache
                 hip.gemm(x, w3[D:], st.self_kv[l, :, t], B, 2 * D, D, lda=D, ldb=D, ldc=st.cap * 2 * D, bias=b3[D:])
                 ctx = self._gen_attend(st, "self", st.q, st.self_kv[l], t + 1)
-                lin(ctx, self._w(p + "self_attn.out_proj.weight"), self._f(p + "self_attn.out_proj.bias"), st.y, D, D)
+                self._linear(ctx, self._w(p + "self_attn.out_proj.weight"), self._f(p + "self_attn.out_proj.bias"), out=st.y)
                 hip.layernorm_fwd(st.y, h, self._f(p + "encoder_attn_layer_norm.weight"), self._f(p + "encoder_attn_layer_norm.bias"), h2, x)
                 h, h2 = h2, h
-                lin(x, self._w(p + "encoder_attn.q_proj.weight"), self._f(p + "encoder_attn.q_proj.bias"), st.q, D, D)
+                self._linear(x, self._w(p + "encoder_attn.q_proj.weight"), self._f(p + "encoder_attn.q_proj.bias"), out=st.q)
                 ctx = self._gen_attend(st, "cross", st.q, st.cross_kv[l].view(st.B, st.S, 2 * D), st.S)
-                lin(ctx, self._w(p + "encoder_attn.out_proj.weight"), self._f(p + "encoder_attn.out_proj.bias"), st.y, D, D)
+                self._linear(ctx, self._w(p + "encoder_attn.out_proj.weight"), self._f(p + "encoder_attn.out_proj.bias"), out=st.y)
                 hip.layernorm_fwd(st.y, h, self._f(p + "final_layer_norm.weight"), self._f(p + "final_layer_norm.bias"), h2, x)
                 h, h2 = h2, h
-                lin(x, self._w(p + "fc1.weight"), self._f(p + "fc1.bias"), st.f, F, D, hip.EPI_GELU)
-                lin(st.f, self._w(p + "fc2.weight"), self._f(p + "fc2.bias"), st.y, D, F)
+                self._linear(x, self._w(p + "fc1.weight"), self._f(p + "fc1.bias"), hip.EPI_GELU, out=st.f)
+                self._linear(st.f, self._w(p + "fc2.weight"), self._f(p + "fc2.bias"), out=st.y)
                 nxt = f"layers.{l + 1}.self_attn_layer_norm." if l + 1 < cfg.decoder_layers else "layer_norm."
                 hip.layernorm_fwd(st.y, h, self._f(nxt + "weight"), self._f(nxt + "bias"), h2, x)
                 h, h2 = h2, h
@@ -744,39 +833,24 @@ class WhisperSeq2Seq(WhisperTrainMixin):
             logits = self._gen_step(st, h_next)
         return i + 1
 
-    def _generate_beam(self, st: _GenState, logits: torch.Tensor, P: int, n_max: int, eos: int, pad: int, sup, bsup, ts, poll_every: int,
-                       length_penalty, no_speech) -> GenerateResult:
+    def _generate_beam(self, st: _GenState, logits: torch.Tensor, pl: _GenPlan, poll_every: int, length_penalty, no_speech) -> GenerateResult:
         """The loop of :meth:`generate` with ``beam_size``: lock step over B * nb rows, the host polls ``n_unfinished`` (audios that
         do not hold nb finished sequences yet), one copy at the end, finalisation and ranking on the host."""
         B, nb = st.B, st.group
-        bs = self._beam_begin(st, P, n_max, eos, pad, sup, bsup, ts)
+        bs = self._beam_begin(st, pl.P, pl.n_max, pl.eos, pl.pad, pl.sup, pl.bsup, pl.ts)
         with torch.cuda.device(self.device):
-            steps = self._gen_loop(st, logits.repeat_interleave(nb, dim=0), n_max, poll_every,
+            steps = self._gen_loop(st, logits.repeat_interleave(nb, dim=0), pl.n_max, poll_every,
                                    lambda logits, i, last: self._beam_step(st, bs, logits, last=last), bs.n_unf, bs.h_next)
             host = lambda x: x.cpu().numpy()
             tok, lp, sums = host(bs.tokens).reshape(B, nb, -1), host(bs.logprobs).reshape(B, nb, -1), host(bs.sums)
             ftok, flp, flen, fsum, nfin = host(bs.fin_tokens), host(bs.fin_logprobs), host(bs.fin_len), host(bs.fin_sum), host(bs.n_fin)
             if no_speech is not None:
                 no_speech = np.exp(no_speech.double().cpu().numpy())
-        beams, beam_lps, chosen, chosen_lp, chosen_sum = [], [], [], [], []
-        for b in range(B):
-            cands = beam_finalize(tok[b], sums[b], ftok[b], flen[b], fsum[b], nfin[b], steps, nb)
-            w = beam_rank(cands, length_penalty)
-            lps = [(flp[b, k, :flen[b, k]] if fin else lp[b, k, :steps] if k >= 0 else lp[b, 0, :0]).astype(np.float64) for _, _, fin, k in cands]
-            beams.append([(c[0], c[1]) for c in cands])
-            beam_lps.append(lps)
-            chosen.append(cands[w][0])
-            chosen_sum.append(cands[w][1])
-            chosen_lp.append(lps[w])
-        lens = np.array([len(c) for c in chosen], dtype=np.int64)
-        n = int(lens.max())
-        tok_a, lp_a = np.full((B, n), pad, dtype=np.int32), np.zeros((B, n), dtype=np.float64)
-        for b in range(B):
-            tok_a[b, :lens[b]] = chosen[b]
-            lp_a[b, :lens[b]] = chosen_lp[b]
-        s = np.array(chosen_sum, dtype=np.float64)
-        return GenerateResult(tokens=chosen, lens=lens, token_array=tok_a, logprobs=lp_a, sum_logprob=s, avg_logprob=s / (lens + 1), steps=steps,
-                              no_speech_prob=no_speech, beams=beams, beam_logprobs=beam_lps)
+        beams = [beam_finalize(tok[b], sums[b], ftok[b], flen[b], fsum[b], nfin[b], steps, nb) for b in range(B)]
+        lps = [[(flp[b, k, :flen[b, k]] if fin else lp[b, k, :steps] if k >= 0 else lp[b, 0, :0]).astype(np.float64) for _, _, fin, k in cands]
+               for b, cands in enumerate(beams)]
+        return GenerateResult(steps=steps, no_speech_prob=no_speech, beams=[[(c[0], c[1]) for c in cands] for cands in beams], beam_logprobs=lps,
+                              **_rank_and_pack(beams, lps, pl.pad, length_penalty))
 
     def _token_mask(self, ids, what: str) -> Optional[torch.Tensor]:
         """A list of token ids -> the uint8 [V] device mask ``ssak_dec_greedy_step`` reads (None for an empty list)."""
@@ -812,6 +886,74 @@ class WhisperSeq2Seq(WhisperTrainMixin):
         if not cfg.task_to_id or task not in cfg.task_to_id:
             raise ValueError(f"task {task!r}: the model folder's task_to_id is {cfg.task_to_id}")
         return np.array([[cfg.decoder_start_token_id, codes[c], cfg.task_to_id[task]] + tail for c in langs], dtype=np.int64)
+
+    def _gen_plan(self, B: int, prompt, language, task, max_new_tokens, suppress_tokens, begin_suppress_tokens, eos_token_id, poll_every: int,
+                  timestamps: bool, beam_size, length_penalty, temperature: float, best_of) -> _GenPlan:
+        """The arguments of :meth:`generate` for ``B`` utterances, validated and normalised; launches nothing (the two masks are uploaded)."""
+        cfg = self.config
+        if not temperature >= 0.0 or temperature == float("inf"):
+            raise ValueError(f"temperature {temperature}: a finite value >= 0 is expected")
+        n_samp = 0
+        if temperature > 0.0:
+            if beam_size is not None:
+                raise ValueError("beam_size with temperature > 0: whisper samples there instead of searching; pass best_of")
+            n_samp = 1 if best_of is None else int(best_of)
+            if not 1 <= n_samp <= 8:
+                raise ValueError(f"best_of {best_of}: 1 to 8 candidates per utterance are built")
+        if beam_size is not None:
+            beam_size = int(beam_size)
+            if not 1 <= beam_size <= 8:
+                raise ValueError(f"beam_size {beam_size}: 1 to 8 hypotheses per utterance are built")
+        elif length_penalty is not None and not n_samp:
+            raise ValueError("length_penalty ranks the candidates of a beam search or of best_of samples: pass beam_size, or temperature and best_of")
+        if timestamps and cfg.no_timestamps_token_id is None:
+            raise ValueError("timestamps=True: the model folder names no no_timestamps_token_id (generation_config.json), the timestamp ids are "
+                             "those above it")
+        if beam_size is not None and B * beam_size > 65535:
+            raise ValueError(f"{B} utterances x beam_size {beam_size} = {B * beam_size} decoder rows: at most 65535 in one call")
+        if B * n_samp > 65535:
+            raise ValueError(f"{B} utterances x best_of {n_samp} = {B * n_samp} decoder rows: at most 65535 in one call")
+        V, maxp = cfg.vocab_size, cfg.max_target_positions
+        eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
+        if eos is None:
+            raise ValueError("no eos_token_id: the model folder names none, pass eos_token_id=")
+        pad = eos if cfg.pad_token_id is None else int(cfg.pad_token_id)
+        # the default prompt is [<|startoftranscript|>, language, task, <|notimestamps|>]: where the language is to be detected only its
+        # width is known yet
+        if prompt is None and language is None and bool(cfg.lang_to_id):
+            if not cfg.task_to_id or task not in cfg.task_to_id or cfg.no_timestamps_token_id is None:
+                raise ValueError(f"task {task!r} / no_timestamps_token_id: the model folder's generation_config.json names neither: pass prompt=")
+            P = 3 if timestamps else 4
+        else:
+            if prompt is None:
+                prompt = self.default_prompt(B, language, task, timestamps)
+            prompt = np.asarray(prompt.cpu() if torch.is_tensor(prompt) else prompt, dtype=np.int64)
+            prompt = np.ascontiguousarray(np.broadcast_to(prompt, (B, prompt.shape[-1])) if prompt.ndim == 1 else prompt)
+            if prompt.ndim != 2 or prompt.shape[0] != B or prompt.shape[1] < 1:
+                raise ValueError(f"prompt [B, P] or [P] for {B} utterances, got shape {prompt.shape}")
+            P = prompt.shape[1]
+        n_max = (min(maxp // 2, maxp - P) if timestamps else maxp - P) if max_new_tokens is None else int(max_new_tokens)
+        if n_max < 1 or P + n_max > maxp:
+            raise ValueError(f"prompt of {P} + max_new_tokens {n_max} tokens: the decoder has max_target_positions = {maxp} positions")
+        if poll_every < 0:
+            raise ValueError("poll_every must be >= 0")
+        pl = _GenPlan(prompt=prompt, P=P, n_max=n_max, eos=eos, pad=pad, best_of=n_samp, group=max(n_samp, 1) if beam_size is None else beam_size,
+                      sup=self._token_mask(cfg.suppress_tokens if suppress_tokens is None else suppress_tokens, "suppress_tokens"),
+                      bsup=self._token_mask(cfg.begin_suppress_tokens if begin_suppress_tokens is None else begin_suppress_tokens,
+                                            "begin_suppress_tokens"))
+        if timestamps:
+            sot = cfg.decoder_start_token_id  # (the default prompt starts with it)
+            sot_rows = [0] if prompt is None else [int(np.argmax(r == sot)) if (r == sot).any() else -1 for r in prompt]
+            if min(sot_rows) < 0 or len(set(sot_rows)) != 1:
+                raise ValueError("timestamps=True: no_speech_prob is read at the prompt's <|startoftranscript|>, which must sit at one position "
+                                 "in every row")
+            pl.sot_row = sot_rows[0]
+            pl.no_speech_id = int(cfg.no_timestamps_token_id) - 1 if cfg.no_speech_token_id is None else int(cfg.no_speech_token_id)
+            if not 0 <= pl.no_speech_id < V:
+                raise ValueError(f"no_speech_token_id {pl.no_speech_id} outside [0, {V})")
+            pl.ts = dict(ts_begin=int(cfg.no_timestamps_token_id) + 1, no_timestamps_id=int(cfg.no_timestamps_token_id),
+                         max_initial=-1 if cfg.max_initial_timestamp_index is None else int(cfg.max_initial_timestamp_index))
+        return pl
 
     def generate(self, enc_or_audio, prompt=None, language=None, task: str = "transcribe", max_new_tokens: Optional[int] = None, enc_lens=None,
                  suppress_tokens=None, begin_suppress_tokens=None, eos_token_id: Optional[int] = None, poll_every: int = 8,
@@ -850,126 +992,47 @@ class WhisperSeq2Seq(WhisperTrainMixin):
         ``GenerateResult.samples`` lists them all.  The same ``seed`` gives the same result.  ``beam_size`` together with
         ``temperature > 0`` is refused (whisper drops the beam there; :func:`ssak_amd.whisper_transcribe.transcribe` does the
         dropping).  ``temperature = 0`` (the default) leaves the call as it was and ignores ``best_of`` and ``seed``."""
-        cfg = self.config
-        timestamps = bool(timestamps)
-        temperature = float(temperature)
-        if not temperature >= 0.0 or temperature == float("inf"):
-            raise ValueError(f"temperature {temperature}: a finite value >= 0 is expected")
-        n_samp = 0  # decoder rows per utterance when sampling; 0: not sampling
-        if temperature > 0.0:
-            if beam_size is not None:
-                raise ValueError("beam_size with temperature > 0: whisper samples there instead of searching; pass best_of")
-            n_samp = 1 if best_of is None else int(best_of)
-            if not 1 <= n_samp <= 8:
-                raise ValueError(f"best_of {best_of}: 1 to 8 candidates per utterance are built")
-        if beam_size is not None:
-            beam_size = int(beam_size)
-            if not 1 <= beam_size <= 8:
-                raise ValueError(f"beam_size {beam_size}: 1 to 8 hypotheses per utterance are built")
-        elif length_penalty is not None and not n_samp:
-            raise ValueError("length_penalty ranks the candidates of a beam search or of best_of samples: pass beam_size, or temperature and best_of")
-        if timestamps and cfg.no_timestamps_token_id is None:
-            raise ValueError("timestamps=True: the model folder names no no_timestamps_token_id (generation_config.json), the timestamp ids are "
-                             "those above it")
         enc = self._as_enc(enc_or_audio)
-        B = enc.shape[0]
-        if beam_size is not None and B * beam_size > 65535:
-            raise ValueError(f"{B} utterances x beam_size {beam_size} = {B * beam_size} decoder rows: at most 65535 in one call")
-        if B * n_samp > 65535:
-            raise ValueError(f"{B} utterances x best_of {n_samp} = {B * n_samp} decoder rows: at most 65535 in one call")
-        V, maxp = cfg.vocab_size, cfg.max_target_positions
-        eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
-        if eos is None:
-            raise ValueError("no eos_token_id: the model folder names none, pass eos_token_id=")
-        pad = eos if cfg.pad_token_id is None else int(cfg.pad_token_id)
-        # the language pass of the default prompt reads the call's cross k|v buffer, so the prompt is built after _gen_begin;
-        # its width is known before: [<|startoftranscript|>, language, task, <|notimestamps|>]
-        detect = prompt is None and language is None and bool(cfg.lang_to_id)
-        if detect:
-            if not cfg.task_to_id or task not in cfg.task_to_id or cfg.no_timestamps_token_id is None:
-                raise ValueError(f"task {task!r} / no_timestamps_token_id: the model folder's generation_config.json names neither: pass prompt=")
-            P = 3 if timestamps else 4
-        else:
-            if prompt is None:
-                prompt = self.default_prompt(B, language, task, timestamps)
-            prompt = np.asarray(prompt.cpu() if torch.is_tensor(prompt) else prompt, dtype=np.int64)
-            prompt = np.ascontiguousarray(np.broadcast_to(prompt, (B, prompt.shape[-1])) if prompt.ndim == 1 else prompt)
-            if prompt.ndim != 2 or prompt.shape[0] != B or prompt.shape[1] < 1:
-                raise ValueError(f"prompt [B, P] or [P] for {B} utterances, got shape {prompt.shape}")
-            P = prompt.shape[1]
-        n_max = (min(maxp // 2, maxp - P) if timestamps else maxp - P) if max_new_tokens is None else int(max_new_tokens)
-        if n_max < 1 or P + n_max > maxp:
-            raise ValueError(f"prompt of {P} + max_new_tokens {n_max} tokens: the decoder has max_target_positions = {maxp} positions")
-        if poll_every < 0:
-            raise ValueError("poll_every must be >= 0")
-        sup = self._token_mask(cfg.suppress_tokens if suppress_tokens is None else suppress_tokens, "suppress_tokens")
-        bsup = self._token_mask(cfg.begin_suppress_tokens if begin_suppress_tokens is None else begin_suppress_tokens, "begin_suppress_tokens")
-        st = self._gen_begin(enc, enc_lens, cap=P + n_max, group=max(n_samp, 1) if beam_size is None else beam_size)
-        if detect:
+        B, V = enc.shape[0], self.config.vocab_size
+        pl = self._gen_plan(B, prompt, language, task, max_new_tokens, suppress_tokens, begin_suppress_tokens, eos_token_id, poll_every,
+                            bool(timestamps), beam_size, length_penalty, float(temperature), best_of)
+        st = self._gen_begin(enc, enc_lens, cap=pl.P + pl.n_max, group=pl.group)
+        prompt = pl.prompt
+        if prompt is None:  # (the language pass reads this call's cross k|v buffer)
             prompt = self.default_prompt(B, self._detect_language(enc, st.enc_lens_host, cross_kv=st.cross_kv)[0], task, timestamps)
         no_speech = None
-        if timestamps:
-            ts_begin = int(cfg.no_timestamps_token_id) + 1
-            max_initial = -1 if cfg.max_initial_timestamp_index is None else int(cfg.max_initial_timestamp_index)
-            ns_id = int(cfg.no_timestamps_token_id) - 1 if cfg.no_speech_token_id is None else int(cfg.no_speech_token_id)
-            sot_rows = [int(np.argmax(r == cfg.decoder_start_token_id)) if (r == cfg.decoder_start_token_id).any() else -1 for r in prompt]
-            if min(sot_rows) < 0 or len(set(sot_rows)) != 1:
-                raise ValueError("timestamps=True: no_speech_prob is read at the prompt's <|startoftranscript|>, which must sit at one position "
-                                 "in every row")
-            if not 0 <= ns_id < V:
-                raise ValueError(f"no_speech_token_id {ns_id} outside [0, {V})")
-            logits, no_speech = self._gen_prefill(st, prompt, also_row=sot_rows[0], also_target=ns_id)
-        else:
+        if pl.ts is None:
             logits = self._gen_prefill(st, prompt)
+        else:
+            logits, no_speech = self._gen_prefill(st, prompt, also_row=pl.sot_row, also_target=pl.no_speech_id)
         if beam_size is not None:
-            ts = dict(ts_begin=ts_begin, no_timestamps_id=int(cfg.no_timestamps_token_id), max_initial=max_initial) if timestamps else None
-            return self._generate_beam(st, logits, P, n_max, eos, pad, sup, bsup, ts, poll_every, length_penalty, no_speech)
+            return self._generate_beam(st, logits, pl, poll_every, length_penalty, no_speech)
         E, Pz = self._w("embed_tokens.weight"), self._w("embed_positions.weight")
         R = B * st.group  # the step's rows: one per utterance, best_of per utterance when sampling
         with torch.cuda.device(self.device):
-            tokens = torch.full((R, n_max), pad, dtype=torch.int32, device=self.device)
-            logprobs = torch.zeros((R, n_max), dtype=torch.float32, device=self.device)
+            tokens = torch.full((R, pl.n_max), pl.pad, dtype=torch.int32, device=self.device)
+            logprobs = torch.zeros((R, pl.n_max), dtype=torch.float32, device=self.device)
             finished = torch.zeros(R, dtype=torch.uint8, device=self.device)
             n_unf = torch.zeros(1, dtype=torch.int32, device=self.device)
             h_next = torch.empty((R, st.D), dtype=torch.bfloat16, device=self.device)
             step, rules = hip.dec_greedy_step, {}
-            if timestamps:
+            if pl.ts is not None:
                 step = hip.dec_timestamp_step
-                rules = dict(ts_begin=ts_begin, no_timestamps_id=cfg.no_timestamps_token_id, max_initial=max_initial,
-                             ts_last=torch.full((R,), -1, dtype=torch.int32, device=self.device))
-            if n_samp:
+                rules = dict(pl.ts, ts_last=torch.full((R,), -1, dtype=torch.int32, device=self.device))
+            if pl.best_of:
                 step = hip.dec_sample_step
                 rules.update(temperature=temperature, seed=sample_call_seed(seed))
-                if n_samp > 1:
-                    logits = logits.repeat_interleave(n_samp, dim=0)
+                if pl.best_of > 1:
+                    logits = logits.repeat_interleave(pl.best_of, dim=0)
             select = lambda logits, i, last: step(logits, V, finished=finished, n_unfinished=n_unf, tokens=tokens, logprobs=logprobs, t=i,
-                                                  eos_id=eos, pad_id=pad, suppress=sup, begin_suppress=bsup, first=i == 0, embed_tokens=E,
-                                                  embed_positions=Pz, next_pos=P + i, h_next=None if last else h_next, **rules)
-            steps = self._gen_loop(st, logits, n_max, poll_every, select, n_unf, h_next)
+                                                  eos_id=pl.eos, pad_id=pl.pad, suppress=pl.sup, begin_suppress=pl.bsup, first=i == 0,
+                                                  embed_tokens=E, embed_positions=Pz, next_pos=pl.P + i, h_next=None if last else h_next, **rules)
+            steps = self._gen_loop(st, logits, pl.n_max, poll_every, select, n_unf, h_next)
             tok = tokens[:, :steps].cpu().numpy()
             lp = logprobs[:, :steps].double().cpu().numpy()
             if no_speech is not None:
                 no_speech = np.exp(no_speech.double().cpu().numpy())
-        lens = np.array([int(np.argmax(r == eos)) + 1 if (r == eos).any() else steps for r in tok], dtype=np.int64)
-        samples = sample_lps = sums = None
-        if n_samp:  # the candidates of an utterance in row order; the ranking's choice fills the other fields
-            sums = lp.sum(-1)  # (a finished row's log-probs are 0 already)
-            samples, sample_lps, pick = [], [], []
-            for b in range(B):
-                rows = range(b * n_samp, (b + 1) * n_samp)
-                cands = [(tok[r, :lens[r]].tolist(), float(sums[r]), bool((tok[r] == eos).any()), r) for r in rows]
-                samples.append([(c[0], c[1]) for c in cands])
-                sample_lps.append([lp[r, :lens[r]].copy() for r in rows])
-                pick.append(rows[beam_rank(cands, length_penalty)])
-            tok, lp, lens, sums = tok[pick], lp[pick], lens[pick], sums[pick]
-        n = int(lens.max())
-        tok, lp = tok[:, :n].copy(), lp[:, :n].copy()
-        for b in range(B):  # (a finished row emits pad with log-probability 0 already; this also covers pad == eos)
-            tok[b, lens[b]:] = pad
-            lp[b, lens[b]:] = 0.0
-        s = lp.sum(-1) if sums is None else sums  # (sampling: the chosen candidates' sums as ``samples`` lists them)
-        return GenerateResult(tokens=[tok[b, :lens[b]].tolist() for b in range(B)], lens=lens, token_array=tok, logprobs=lp, sum_logprob=s,
-                              avg_logprob=s / (lens + 1), steps=steps, no_speech_prob=no_speech, samples=samples, sample_logprobs=sample_lps)
+        return GenerateResult(steps=steps, no_speech_prob=no_speech, **rows_finalize(tok, lp, steps, pl.eos, pl.pad, pl.best_of, length_penalty))
 
     def transcribe(self, waveforms, language=None, task: str = "transcribe", no_speech_threshold: Optional[float] = 0.6,
                    logprob_threshold: Optional[float] = -1.0, batch_size: int = 8, **kw):

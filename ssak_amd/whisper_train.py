@@ -1,18 +1,16 @@
 """Full fine-tuning of ``WhisperForConditionalGeneration`` (the reference's non-PEFT branch,
 ssak/train/transformers/whisper_train.py:432,464-507,531) on one MI355X: the training half of :class:`ssak_amd.whisper_seq2seq.WhisperSeq2Seq`.
 
-:class:`WhisperTrainMixin` gives the model ``forward_train`` (the teacher-forced walk of ``_decoder_hidden`` with everything saved
-that the backward reads, HF's ``.loss`` on the device), ``backward`` (the vocabulary projection per ``row_chunk`` rows, the layers in
-reverse, the tied embedding's two gradients, the cross k|v gradients into one fp32 ``d_enc`` handed to the encoder engine's
-``backward_hidden``) and ``save_pretrained``.  :class:`WhisperAdamW` clips the encoder's and the decoder's gradient buffers by one
+:class:`WhisperTrainMixin` gives the model ``forward_train`` (``_decoder_hidden(keep=)``, the model's one teacher-forced pass keeping
+what the backward reads -- its docstring lists that -- and HF's ``.loss`` on the device), ``backward`` (the vocabulary projection
+per ``row_chunk`` rows, the layers in reverse, the tied embedding's two gradients, the cross k|v gradients into one fp32 ``d_enc``
+handed to the encoder engine's ``backward_hidden``) and ``save_pretrained``.  :class:`WhisperAdamW` clips the encoder's and the decoder's gradient buffers by one
 global norm and steps both.  Kernels: ssak_amd/csrc/whisper_train.hip (ABI 650) for the attention, cross-entropy and embedding
 backward, ``ssak_layernorm_fwd_stats`` / ``ssak_layernorm_bwd``, and ``ssak_gemm_bf16`` for every product (dgrad; wgrad with both
 operands K-major, ``accumulate`` and a library-sized split; the GELU pair of fc1 / fc2), ``ssak_colsum_bf16`` for the bias sums.
 Every sum has a fixed order: two steps from the same state give the same bits.
 
-What is saved per layer (bf16 unless noted): the residual stream at each of the three LayerNorms with their mean / rstd (fp32), the
-three LayerNorm outputs, the packed q|k|v, the cross q and k|v, both attention outputs with their log-sum-exp (fp32), fc1's
-pre-activation and its GELU.  Not built: decoder dropout / layerdrop (refused by name; every published Whisper config has them at
+Not built: decoder dropout / layerdrop (refused by name; every published Whisper config has them at
 0), gradient checkpointing, gradient accumulation, LoRA / int8 / int4, data parallelism.
 """
 from __future__ import annotations
@@ -33,6 +31,7 @@ from .trainer import decay_ranges, hf_decays, linear_warmup_lr
 # bound the inference workspace leave the step on small-M products (tools/bench_whisper_train.py times both); 2048 rows are 425 MB
 # of fp32 logits and 212 MB of bf16 dlogits.
 TRAIN_ROW_CHUNK = 2048
+_QKV = ("q_proj", "k_proj", "v_proj")  # the order in which the layout packs an attention's projections
 _REGULARISERS = ("dropout", "attention_dropout", "activation_dropout", "decoder_layerdrop", "encoder_layerdrop")
 # what from_pretrained() takes from generation_config.json
 _GENERATION_KEYS = ("lang_to_id", "decoder_start_token_id", "eos_token_id", "pad_token_id", "suppress_tokens", "begin_suppress_tokens",
@@ -105,10 +104,7 @@ class WhisperTrainMixin:
             if float(getattr(cfg, name, 0.0) or 0.0) > 0.0:
                 raise ValueError(f"{name} = {getattr(cfg, name)}: training with {name} > 0 is not built (every published Whisper "
                                  f"configuration has it at 0)")
-        lab = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
-        if lab.ndim != 2 or lab.shape[1] < 1:
-            raise ValueError(f"labels [B, L], got shape {lab.shape}")
-        lab = np.ascontiguousarray(lab, dtype=np.int64)
+        lab = self._ids(labels, "labels")
         B, L = lab.shape
         if L > cfg.max_target_positions:
             raise ValueError(f"{L} label positions, the decoder has {cfg.max_target_positions}")
@@ -131,54 +127,17 @@ class WhisperTrainMixin:
         Bx, S, D = enc.shape
         if Bx != B:
             raise ValueError(f"{B} label sequences for {Bx} encoder outputs")
-        lens_host = None
-        if enc_lens is not None:
-            lens_host = hip._host_i32(enc_lens, B, "enc_lens")
-            if lens_host.min() < 1 or lens_host.max() > S:
-                raise ValueError(f"enc_lens: {B} values in [1, {S}] expected, got {lens_host}")
+        lens_host = self._enc_lens(enc_lens, B, S)
 
-        nh, N = cfg.decoder_attention_heads, B * L
-        dev = self.device
-        bf = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=dev)
-        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        enc2 = enc.reshape(B * S, D)
-        layers = []
-        with torch.cuda.device(dev):
-            def norm(y, res, name):
-                """r = res + y, LayerNorm ``name`` of it -> (r, out, mean, rstd)"""
-                r = res if y is None else bf(N, D)
-                out, mean, rstd = bf(N, D), f32(N), f32(N)
-                hip.layernorm_fwd_stats(y, res, self._f(name + ".weight"), self._f(name + ".bias"), out, mean, rstd, r_out=None if y is None else r)
-                return r, out, mean, rstd
-
-            h = hip.dec_embed(self._w("embed_tokens.weight"), self._w("embed_positions.weight"), ids, 0)
-            ln = norm(None, h, "layers.0.self_attn_layer_norm")
-            for l in range(cfg.decoder_layers):
-                p = f"layers.{l}."
-                s = {"ln1": ln}
-                s["qkv"] = qkv = self._linear(ln[1], self._w(p + "self_attn.q_proj.weight", 3), self._f(p + "self_attn.q_proj.bias", 3))
-                s["ctx_s"], s["lse_s"] = hip.dec_attention_fwd_lse(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, L, L, nh, causal=True)
-                y = self._linear(s["ctx_s"], self._w(p + "self_attn.out_proj.weight"), self._f(p + "self_attn.out_proj.bias"))
-                s["ln2"] = ln = norm(y, ln[0], p + "encoder_attn_layer_norm")
-                s["q_c"] = self._linear(ln[1], self._w(p + "encoder_attn.q_proj.weight"), self._f(p + "encoder_attn.q_proj.bias"))
-                s["kv_c"] = kv = self._linear(enc2, self._w(p + "encoder_attn.k_proj.weight", 2), self._f(p + "encoder_attn.k_proj.bias", 2))
-                s["ctx_c"], s["lse_c"] = hip.dec_attention_fwd_lse(s["q_c"], kv[:, :D], kv[:, D:], B, L, S, nh, klens=lens_host)
-                y = self._linear(s["ctx_c"], self._w(p + "encoder_attn.out_proj.weight"), self._f(p + "encoder_attn.out_proj.bias"))
-                s["ln3"] = ln = norm(y, ln[0], p + "final_layer_norm")
-                F = cfg.decoder_ffn_dim
-                s["pre"], s["f"] = bf(N, F), bf(N, F)
-                hip.gemm(ln[1], self._w(p + "fc1.weight"), s["f"], N, F, D, lda=D, ldb=D, ldc=F, bias=self._f(p + "fc1.bias"), epilogue=hip.EPI_GELU,
-                         aux_out=s["pre"])
-                y = self._linear(s["f"], self._w(p + "fc2.weight"), self._f(p + "fc2.bias"))
-                nxt = f"layers.{l + 1}.self_attn_layer_norm" if l + 1 < cfg.decoder_layers else "layer_norm"
-                ln = norm(y, ln[0], nxt)
-                layers.append(s)
-            targets = np.ascontiguousarray(lab.reshape(-1), dtype=np.int32)
-            parts = [hip.token_logprobs(logits, cfg.vocab_size, targets[r0:r0 + n])[1] for r0, n, logits in self._project_chunks(ln[1])]
+        layers = []  # (validation runs the keeping entries too and drops what they kept)
+        ln_f = self._decoder_hidden(enc, ids, lens_host, keep=layers)
+        targets = np.ascontiguousarray(lab.reshape(-1), dtype=np.int32)
+        with torch.cuda.device(self.device):
+            parts = [hip.token_logprobs(logits, cfg.vocab_size, targets[r0:r0 + n])[1] for r0, n, logits in self._project_chunks(ln_f[1])]
             lp = parts[0] if len(parts) == 1 else torch.cat(parts)
             loss = -(lp.sum(dtype=torch.float32) / n_scored).reshape(1)
-        self._train = None if not keep_graph else dict(B=B, L=L, S=S, enc2=enc2, enc_lens=lens_host, ids=ids, targets=targets, n_scored=n_scored, layers=layers, ln_f=ln,
-                           train_encoder=train_encoder)
+        self._train = None if not keep_graph else dict(B=B, L=L, S=S, enc2=enc.reshape(B * S, D), enc_lens=lens_host, ids=ids, targets=targets,
+                                                       n_scored=n_scored, layers=layers, ln_f=ln_f, train_encoder=train_encoder)
         return loss
 
     # ------------------------------------------------------------------ backward
@@ -200,6 +159,20 @@ class WhisperTrainMixin:
         M, No = dy.shape
         ws = hip._ws(hip.lib.ssak_colsum_workspace_bytes(No), self.device)
         hip.check(hip.lib.ssak_colsum_bf16(hip.ptr(dy), dy.stride(0), M, No, hip.ptr(db), hip.ptr(ws), ws.numel(), hip.stream()))
+
+    def _linear_bwd(self, dy: torch.Tensor, x: torch.Tensor, name: str, rows: int = 1, **dgrad):
+        """The three gradients of nn.Linear ``name`` (y = x W^T + b) from ``dy``: dW += dY^T X, db = colsum(dY), -> dX = dY W
+        (``dgrad``: what the input-gradient product takes on top -- ``out``, ``accumulate``, an epilogue).  ``rows`` = 3 / 2: the packed
+        q|k|v / k|v product whose first projection ``name`` is -- one weight gradient and one input gradient over the packed matrix,
+        the bias sums per column block.  Whisper's k_proj has no bias: its synthetic slot gets no gradient."""
+        self._wgrad(dy, x, self._g(name + ".weight", rows))
+        attn, _, proj = name.rpartition(".")
+        blocks = [name] if rows == 1 else [f"{attn}.{q}" for q in _QKV[_QKV.index(proj):][:rows]]
+        n = dy.shape[1] // rows
+        for i, block in enumerate(blocks):
+            if not block.endswith("k_proj"):
+                self._bgrad(dy[:, i * n:(i + 1) * n], self._g(block + ".bias"))
+        return self._dgrad(dy, self._w(name + ".weight", rows), **dgrad)
 
     def backward(self, grad_scale: float = 1.0):
         """d (grad_scale * loss) / d parameters of the last :meth:`forward_train`: the decoder's into ``dec_grads`` (overwritten), the
@@ -242,41 +215,26 @@ class WhisperTrainMixin:
             for l in reversed(range(nl)):
                 p = f"layers.{l}."
                 sv = s["layers"][l]
-                # feed-forward: dh is the gradient of fc2's output
-                self._wgrad(dh, sv["f"], self._g(p + "fc2.weight"))
-                self._bgrad(dh, self._g(p + "fc2.bias"))
-                dpre = self._dgrad(dh, self._w(p + "fc2.weight"), epilogue=hip.EPI_MUL_GELU_GRAD, aux_in=sv["pre"])
-                self._wgrad(dpre, sv["ln3"][1], self._g(p + "fc1.weight"))
-                self._bgrad(dpre, self._g(p + "fc1.bias"))
-                dh = norm_bwd(self._dgrad(dpre, self._w(p + "fc1.weight")), sv["ln3"], p + "final_layer_norm", dh)
-                # cross-attention
+                # feed-forward: dh is the gradient of fc2's output; its input gradient takes GELU's on the way
+                dpre = self._linear_bwd(dh, sv["f"], p + "fc2", epilogue=hip.EPI_MUL_GELU_GRAD, aux_in=sv["pre"])
+                dh = norm_bwd(self._linear_bwd(dpre, sv["ln3"][1], p + "fc1"), sv["ln3"], p + "final_layer_norm", dh)
+                # cross-attention: the k|v product's input gradient adds to d_enc
                 a = p + "encoder_attn."
-                self._wgrad(dh, sv["ctx_c"], self._g(a + "out_proj.weight"))
-                self._bgrad(dh, self._g(a + "out_proj.bias"))
-                dctx = self._dgrad(dh, self._w(a + "out_proj.weight"))
+                dctx = self._linear_bwd(dh, sv["ctx_c"], a + "out_proj")
                 dq, dkv = bf(N, D), bf(B * S, 2 * D)
                 kv = sv["kv_c"]
                 hip.dec_attention_bwd(sv["q_c"], kv[:, :D], kv[:, D:], sv["ctx_c"], sv["lse_c"], dctx, dq, dkv[:, :D], dkv[:, D:], B, L, S, nh,
                                       klens=s["enc_lens"])
-                self._wgrad(dq, sv["ln2"][1], self._g(a + "q_proj.weight"))
-                self._bgrad(dq, self._g(a + "q_proj.bias"))
-                self._wgrad(dkv, enc2, self._g(a + "k_proj.weight", 2))
-                self._bgrad(dkv[:, D:], self._g(a + "v_proj.bias"))  # (k_proj has no bias: its synthetic slot gets no gradient)
-                hip.gemm(dkv, self._w(a + "k_proj.weight", 2), d_enc, B * S, D, 2 * D, b_kmajor=True, lda=2 * D, ldb=D, ldc=D, accumulate=True)
-                dh = norm_bwd(self._dgrad(dq, self._w(a + "q_proj.weight")), sv["ln2"], p + "encoder_attn_layer_norm", dh)
+                self._linear_bwd(dkv, enc2, a + "k_proj", 2, out=d_enc, accumulate=True)
+                dh = norm_bwd(self._linear_bwd(dq, sv["ln2"][1], a + "q_proj"), sv["ln2"], p + "encoder_attn_layer_norm", dh)
                 # causal self-attention
                 a = p + "self_attn."
-                self._wgrad(dh, sv["ctx_s"], self._g(a + "out_proj.weight"))
-                self._bgrad(dh, self._g(a + "out_proj.bias"))
-                dctx = self._dgrad(dh, self._w(a + "out_proj.weight"))
+                dctx = self._linear_bwd(dh, sv["ctx_s"], a + "out_proj")
                 dqkv = bf(N, 3 * D)
                 qkv = sv["qkv"]
                 hip.dec_attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], sv["ctx_s"], sv["lse_s"], dctx, dqkv[:, :D], dqkv[:, D:2 * D],
                                       dqkv[:, 2 * D:], B, L, L, nh, causal=True)
-                self._wgrad(dqkv, sv["ln1"][1], self._g(a + "q_proj.weight", 3))
-                self._bgrad(dqkv[:, :D], self._g(a + "q_proj.bias"))
-                self._bgrad(dqkv[:, 2 * D:], self._g(a + "v_proj.bias"))
-                dh = norm_bwd(self._dgrad(dqkv, self._w(a + "q_proj.weight", 3)), sv["ln1"], p + "self_attn_layer_norm", dh)
+                dh = norm_bwd(self._linear_bwd(dqkv, sv["ln1"][1], a + "q_proj", 3), sv["ln1"], p + "self_attn_layer_norm", dh)
             # ---- the embedding's other use: the rows gathered per token, the positions summed over the batch
             hip.dec_embed_bwd(dh, s["ids"], dE, self._g("embed_positions.weight"), 0)
             self.encoder_grads_ready = bool(s["train_encoder"])

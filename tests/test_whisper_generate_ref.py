@@ -122,3 +122,67 @@ def test_split_and_combine_softmax(n_keys, n_split):
         assert np.isfinite(got).all() and np.abs(got - want).max() < 1e-12
         if klens is not None:
             assert np.abs(got[1] - v[1, 0]).max() < 1e-15, "one visible key: ctx is its value row"
+
+
+# ------------------------------------------------------------------------------------------------------------ host finalisation
+def _rows(rows, pad):
+    """[(tokens, logprobs)] per row, as long as the longest -> int32 / float64 arrays the way the loop leaves them."""
+    n = max(len(t) for t, _ in rows)
+    tok, lp = np.full((len(rows), n), pad, dtype=np.int32), np.zeros((len(rows), n))
+    for r, (t, l) in enumerate(rows):
+        tok[r, :len(t)], lp[r, :len(l)] = t, l
+    return tok, lp
+
+
+def test_rows_finalize_greedy():
+    """eos mid-row (the row goes on with pad and 0), no eos (length = steps), eos at the first step.  Every log-probability is a small
+    dyadic number, so every sum below is exact."""
+    from ssak_amd.whisper_seq2seq import rows_finalize
+    eos, pad = 9, 0
+    tok, lp = _rows([([5, 6, eos, pad, pad], [-0.5, -0.25, -1.0]), ([3, 4, 5, 6, 7], [-0.5] * 5), ([eos, pad, pad, pad, pad], [-2.0])], pad)
+    out = rows_finalize(tok, lp, 5, eos, pad)
+    assert out["tokens"] == [[5, 6, eos], [3, 4, 5, 6, 7], [eos]] and out["lens"].tolist() == [3, 5, 1] and out["lens"].dtype == np.int64
+    assert out["token_array"].dtype == np.int32 and out["token_array"].tolist() == [[5, 6, eos, pad, pad], [3, 4, 5, 6, 7], [eos, pad, pad, pad, pad]]
+    assert out["logprobs"].dtype == np.float64 and out["logprobs"].tolist() == [[-0.5, -0.25, -1.0, 0, 0], [-0.5] * 5, [-2.0, 0, 0, 0, 0]]
+    assert out["sum_logprob"].tolist() == [-1.75, -2.5, -2.0] and out["avg_logprob"].tolist() == [-1.75 / 4, -2.5 / 6, -1.0]
+    assert "samples" not in out and "sample_logprobs" not in out
+    # fewer steps than the arrays are wide (the loop stopped early): nothing past them is read; the arrays are as wide as the longest row
+    out = rows_finalize(tok, lp, 2, eos, pad)
+    assert out["tokens"] == [[5, 6], [3, 4], [eos]] and out["sum_logprob"].tolist() == [-0.75, -1.0, -2.0]
+    assert out["token_array"].tolist() == [[5, 6], [3, 4], [eos, pad]]
+
+
+def test_rows_finalize_pad_is_eos():
+    """pad == eos: the row ends with its FIRST eos; the pads after it are no tokens, and a log-probability left past the end is dropped."""
+    from ssak_amd.whisper_seq2seq import rows_finalize
+    eos = pad = 9
+    tok, lp = _rows([([5, eos, eos, eos], [-0.5, -0.25, -8.0]), ([1, 2, 3, eos], [-1.0] * 4)], pad)
+    out = rows_finalize(tok, lp, 4, eos, pad)
+    assert out["tokens"] == [[5, eos], [1, 2, 3, eos]] and out["lens"].tolist() == [2, 4]
+    assert out["token_array"].tolist() == [[5, eos, pad, pad], [1, 2, 3, eos]]
+    assert out["logprobs"].tolist() == [[-0.5, -0.25, 0, 0], [-1.0] * 4] and out["sum_logprob"].tolist() == [-0.75, -4.0]
+
+
+def test_rows_finalize_best_of():
+    """Two utterances x three rows, score = sum / tokens before eos.  Utterance 0: -1 / 1, -0.75 / 3, -2 / 2 -> the middle row, under
+    every ``length_penalty`` tried (its sum is the largest too).  Utterance 1: -3 / 4 (no eos), -2 / 1, -1 / 2 -> the last row; with
+    ``length_penalty`` a the scores are sum / ((5 + n) / 6) ** a: a = 1 gives -2, -2, -6 / 7 -> the last; a = 4 gives -0.593, -2,
+    -0.540 -> the last; a = 8 gives -0.117, -2, -0.291 -> the first."""
+    from ssak_amd.whisper_seq2seq import rows_finalize
+    eos, pad = 9, 0
+    rows = [([5, eos], [-0.5, -0.5]), ([5, 6, 7, eos], [-0.25, -0.25, -0.125, -0.125]), ([5, 6, eos], [-1.0, -0.5, -0.5]),
+            ([1, 2, 3, 4], [-0.75] * 4), ([1, eos], [-1.0, -1.0]), ([1, 2, eos], [-0.5, -0.25, -0.25])]
+    tok, lp = _rows(rows, pad)
+    out = rows_finalize(tok, lp, 4, eos, pad, best_of=3)
+    assert out["tokens"] == [[5, 6, 7, eos], [1, 2, eos]] and out["lens"].tolist() == [4, 3]
+    assert out["token_array"].tolist() == [[5, 6, 7, eos], [1, 2, eos, pad]]
+    assert out["logprobs"].tolist() == [[-0.25, -0.25, -0.125, -0.125], [-0.5, -0.25, -0.25, 0]]
+    assert out["sum_logprob"].tolist() == [-0.75, -1.0] and out["avg_logprob"].tolist() == [-0.75 / 5, -0.25]
+    assert out["samples"] == [[(t, float(sum(l))) for t, l in rows[:3]], [(t, float(sum(l))) for t, l in rows[3:]]]
+    assert [[l.tolist() for l in u] for u in out["sample_logprobs"]] == [[l for _, l in rows[:3]], [l for _, l in rows[3:]]]
+    for penalty, want in ((0.0, [[5, 6, 7, eos], [1, 2, eos]]), (1.0, [[5, 6, 7, eos], [1, 2, eos]]), (4.0, [[5, 6, 7, eos], [1, 2, eos]]),
+                          (8.0, [[5, 6, 7, eos], [1, 2, 3, 4]])):
+        assert rows_finalize(tok, lp, 4, eos, pad, best_of=3, length_penalty=penalty)["tokens"] == want, penalty
+    # best_of = 1 lists its one candidate per utterance and sums the whole row
+    one = rows_finalize(tok, lp, 4, eos, pad, best_of=1)
+    assert one["tokens"] == [t for t, _ in rows] and [len(u) for u in one["samples"]] == [1] * 6
