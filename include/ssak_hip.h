@@ -1031,6 +1031,39 @@ int ssak_debug_mel_to_cl(const float* mel, void* cl, int B, int C, int T, int RS
 int ssak_debug_add_rowvec(const void* x, const void* pos, void* out, int B, int F, int H, int dtype, void* stream);
 int ssak_debug_copy_rows_padded(const void* src, void* dst, int B, int F, int RS, int H, int dtype, void* stream);
 
+/* ---- TEST-ONLY entries (ABI 660): the helper kernels the wav2vec2 engine launches between its row kernels and GEMMs
+ * (norm_act.hip, transpose.hip), one k_* call each; no device code of their own ------------------------------------------
+ * dtype 0 = bf16 (the engine), 1 = fp32 (the fp32-exact mode) is the storage type of the void* activations.
+ * specaug_fwd: h [B, F, C] in place: row (b, t) = 0 where t >= flens[b], else = embed [C] (rounded to the storage type) where
+ *   mask [B, F] != 0, else untouched.  mask and flens may each be NULL (both: nothing is launched); a mask needs embed.
+ * specaug_bwd: dembed [C] += the sum of the rows of dh [B, F, C] that are masked and not padding (mask and dembed given), then
+ *   every masked or padding row of dh = 0.  C a multiple of 8.  scratch / scratch_floats as for colsum.
+ * colsum: out [N] += sum over rows m < M of X[m * ld + n] (out is NOT zeroed first, unlike ssak_colsum_bf16); N and ld
+ *   multiples of 8, ld >= N.  With rowmask [M] only rows with rowmask[m] != 0 count, and with flens too (needs rowmask and
+ *   F > 0) only those with m % F < flens[m / F].  A scratch of >= min(64, ceil(M / 32)) * N floats gives the two-stage sum in
+ *   a fixed order; NULL or a smaller one falls back to float atomics into out.
+ * gelu_grad_mul: out = dy * gelu'(pre);  add: out = a + b (fp32 add, rounded to the storage type); n a multiple of 8.
+ * transpose_batched: dst[i] [C[i]][R[i]] = src[i] [R[i]][C[i]]^T, bf16; src, dst, R, C are HOST arrays of n entries (the
+ *   pointers in them device pointers).  Any shape and alignment (the 16-byte path needs R, C multiples of 8 and 16-byte-aligned
+ *   pointers); more than 112 matrices are split over several launches.
+ * reduce: job i is out[i][c] += sum_{k < slots[i]} partial[i][k * stride[i] + c], c < ncols[i] (HOST arrays of n entries;
+ *   stride >= ncols).  The jobs are issued as ncalls consecutive k_reduce calls of call_sizes[c] jobs (1 .. 32 each, adding up
+ *   to n).  use_sink != 0: the calls run under a local deferred-reduction queue (32 jobs) that is flushed once at the end; a
+ *   call the queue has no room for runs at once, whole.  use_sink = 0: every call launches at once.  *queued_out / *direct_out
+ *   (host, may be NULL): how many jobs went each way.  Jobs that share an out are added one after the other.
+ * Bad arguments are SSAK_ERR_INVALID before any launch. */
+int ssak_debug_specaug_fwd(void* h, const uint8_t* mask, const int32_t* flens, const float* embed, int B, int F, int C, int dtype,
+                           void* stream);
+int ssak_debug_specaug_bwd(void* dh, const uint8_t* mask, const int32_t* flens, float* dembed, int B, int F, int C, int dtype, float* scratch,
+                           size_t scratch_floats, void* stream);
+int ssak_debug_colsum(const void* X, long ld, int M, int N, float* out, float* scratch, size_t scratch_floats, const uint8_t* rowmask,
+                      const int32_t* flens, int F, int dtype, void* stream);
+int ssak_debug_gelu_grad_mul(const void* dy, const void* pre, void* out, long n, int dtype, void* stream);
+int ssak_debug_add(const void* a, const void* b, void* out, long n, int dtype, void* stream);
+int ssak_debug_transpose_batched(int n, const void* const* src, void* const* dst, const int* R, const int* C, void* stream);
+int ssak_debug_reduce(int n, const float* const* partial, float* const* out, const long* stride, const int* slots, const int* ncols,
+                      int ncalls, const int* call_sizes, int use_sink, int* queued_out, int* direct_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

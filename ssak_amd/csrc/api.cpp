@@ -18,7 +18,7 @@ void ssak_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int ssak_version(void) { return 650; }  // Whisper training kernels: ssak_dec_attention_bwd, ssak_dec_ce_bwd, ... (INTEGRATION.md "ABI 650")
+extern "C" int ssak_version(void) { return 660; }  // test entries for the engine's helper kernels: ssak_debug_specaug_fwd, ssak_debug_reduce, ... (INTEGRATION.md "ABI 660")
 extern "C" const char* ssak_last_error(void) { return g_err; }
 
 // ---- optional per-launch timing (bench.py's roofline leg): HIP events around launches, on the launch's own stream ----

@@ -8,6 +8,7 @@
 // Dropout masks are recomputed from (seed, stream, element index) in the backward kernels.
 #include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 #include "kernels.h"
@@ -1178,4 +1179,87 @@ extern "C" int ssak_debug_gelu(const float* x, long n, float* y, float* dydx, in
   else debug_gelu_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(x, n, y, dydx);
   SSAK_LAUNCH_CHECK();
   return SSAK_OK;
+}
+
+// ---- debug (ABI 660): the helper kernels the wav2vec2 engine launches between its row kernels and GEMMs, one k_* call each
+// (tests/test_gpu_helpers.py holds them to the float64 restatement tests/helpers_ref.py).  No device code of their own; dtype as
+// above.  Nothing on the hot path calls these.
+extern "C" int ssak_debug_specaug_fwd(void* h, const uint8_t* mask, const int32_t* flens, const float* embed, int B, int F, int C, int dtype,
+                                      void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_specaug_fwd: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(h && B > 0 && F > 0 && C > 0, "debug_specaug_fwd: h null or B=%d F=%d C=%d", B, F, C);
+  SSAK_REQUIRE(!mask || embed, "debug_specaug_fwd: a mask needs the embedding");
+  if (dtype == 0) return k_specaug_fwd_t<bf16>((bf16*)h, mask, flens, embed, B, F, C, (hipStream_t)stream);
+  return k_specaug_fwd_t<float>((float*)h, mask, flens, embed, B, F, C, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_specaug_bwd(void* dh, const uint8_t* mask, const int32_t* flens, float* dembed, int B, int F, int C, int dtype,
+                                      float* scratch, size_t scratch_floats, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_specaug_bwd: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(dh && B > 0 && F > 0 && C > 0 && (C & 7) == 0, "debug_specaug_bwd: dh null or B=%d F=%d C=%d (C a multiple of 8)", B, F, C);
+  if (dtype == 0) return k_specaug_bwd_t<bf16>((bf16*)dh, mask, flens, dembed, B, F, C, (hipStream_t)stream, scratch, scratch_floats);
+  return k_specaug_bwd_t<float>((float*)dh, mask, flens, dembed, B, F, C, (hipStream_t)stream, scratch, scratch_floats);
+}
+
+// k_colsum_t as the engine calls it: out += (it is not zeroed first, unlike ssak_colsum_bf16)
+extern "C" int ssak_debug_colsum(const void* X, long ld, int M, int N, float* out, float* scratch, size_t scratch_floats,
+                                 const uint8_t* rowmask, const int32_t* flens, int F, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_colsum: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(X && out && M > 0 && N > 0 && (N & 7) == 0 && (ld & 7) == 0 && ld >= N,
+               "debug_colsum: null operand or M=%d N=%d ld=%ld (N, ld multiples of 8, ld >= N)", M, N, ld);
+  SSAK_REQUIRE(!flens || (rowmask && F > 0), "debug_colsum: flens needs rowmask and F > 0");
+  if (dtype == 0)
+    return k_colsum_t<bf16>((const bf16*)X, ld, M, N, out, (hipStream_t)stream, scratch, scratch_floats, rowmask, flens, F);
+  return k_colsum_t<float>((const float*)X, ld, M, N, out, (hipStream_t)stream, scratch, scratch_floats, rowmask, flens, F);
+}
+
+extern "C" int ssak_debug_gelu_grad_mul(const void* dy, const void* pre, void* out, long n, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_gelu_grad_mul: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(dy && pre && out && n > 0 && (n & 7) == 0, "debug_gelu_grad_mul: null operand or n=%ld (a positive multiple of 8)", n);
+  if (dtype == 0) return k_gelu_grad_mul_t<bf16>((const bf16*)dy, (const bf16*)pre, (bf16*)out, n, (hipStream_t)stream);
+  return k_gelu_grad_mul_t<float>((const float*)dy, (const float*)pre, (float*)out, n, (hipStream_t)stream);
+}
+
+extern "C" int ssak_debug_add(const void* a, const void* b, void* out, long n, int dtype, void* stream) {
+  SSAK_REQUIRE(dtype == 0 || dtype == 1, "debug_add: dtype %d (0 bf16, 1 fp32)", dtype);
+  SSAK_REQUIRE(a && b && out && n > 0 && (n & 7) == 0, "debug_add: null operand or n=%ld (a positive multiple of 8)", n);
+  if (dtype == 0) return k_add_t<bf16>((const bf16*)a, (const bf16*)b, (bf16*)out, n, (hipStream_t)stream);
+  return k_add_t<float>((const float*)a, (const float*)b, (float*)out, n, (hipStream_t)stream);
+}
+
+// The jobs (host arrays) are cut into ncalls consecutive k_reduce calls of call_sizes[c] jobs.  use_sink: the calls run under a
+// local ReduceSink, as the engine's backward runs its producers, and one k_reduce_flush follows; a call the sink has no room for
+// runs at once.  *queued_out / *direct_out: the jobs that went each way.
+extern "C" int ssak_debug_reduce(int n, const float* const* partial, float* const* out, const long* stride, const int* slots, const int* ncols,
+                                 int ncalls, const int* call_sizes, int use_sink, int* queued_out, int* direct_out, void* stream) {
+  SSAK_REQUIRE(n > 0 && partial && out && stride && slots && ncols, "debug_reduce: n=%d or a null job array", n);
+  SSAK_REQUIRE(ncalls > 0 && call_sizes, "debug_reduce: ncalls=%d or no call sizes", ncalls);
+  long total = 0;
+  for (int c = 0; c < ncalls; ++c) {
+    SSAK_REQUIRE(call_sizes[c] > 0 && call_sizes[c] <= ReduceSink::CAP, "debug_reduce: call %d has %d jobs (1 .. %d)", c, call_sizes[c],
+                 ReduceSink::CAP);
+    total += call_sizes[c];
+  }
+  SSAK_REQUIRE(total == n, "debug_reduce: the call sizes add up to %ld, not n=%d", total, n);
+  std::vector<ReduceJob> jobs((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    SSAK_REQUIRE(partial[i] && out[i] && slots[i] > 0 && ncols[i] > 0 && stride[i] >= ncols[i],
+                 "debug_reduce: job %d: null pointer or slots=%d ncols=%d stride=%ld", i, slots[i], ncols[i], stride[i]);
+    jobs[i] = ReduceJob{partial[i], out[i], stride[i], slots[i], ncols[i]};
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  ReduceSink sink;
+  ReduceSink* const saved = g_reduce_sink;
+  g_reduce_sink = use_sink ? &sink : nullptr;
+  int rc = SSAK_OK, queued = 0, direct = 0;
+  for (int c = 0, first = 0; c < ncalls && rc == SSAK_OK; first += call_sizes[c++]) {
+    const int before = sink.n;
+    rc = k_reduce(jobs.data() + first, call_sizes[c], st);
+    (sink.n == before + call_sizes[c] ? queued : direct) += call_sizes[c];  // (a call is never half queued)
+  }
+  g_reduce_sink = saved;
+  if (queued_out) *queued_out = queued;
+  if (direct_out) *direct_out = direct;
+  if (rc != SSAK_OK || sink.n == 0) return rc;
+  return k_reduce_flush(sink, st);
 }

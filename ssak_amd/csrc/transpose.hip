@@ -90,3 +90,11 @@ int k_transpose_bf16_batched(int n, const bf16* const* src, bf16* const* dst, co
   }
   return SSAK_OK;
 }
+
+// ---- debug (ABI 660): k_transpose_bf16_batched on host arrays of device pointers and shapes (tests/test_gpu_helpers.py: the
+// element-wise path, ragged edge tiles and the split beyond TR_CAP matrices, none of which the engine's weights reach).
+extern "C" int ssak_debug_transpose_batched(int n, const void* const* src, void* const* dst, const int* R, const int* C, void* stream) {
+  SSAK_REQUIRE(n > 0 && src && dst && R && C, "debug_transpose_batched: n=%d or a null array", n);
+  return k_transpose_bf16_batched(n, reinterpret_cast<const bf16* const*>(src), reinterpret_cast<bf16* const*>(dst), R, C,
+                                  (hipStream_t)stream);
+}

@@ -14,7 +14,7 @@ import torch
 
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libssak_hip.so")
 _LIB_PATH = os.environ.get("SSAK_HIP_LIB") or _DEFAULT_LIB  # (the override names another build OF THE SAME ABI: A/B runs, instrumented builds)
-ABI_VERSION = 650  # ssak_version() of the library this binding's struct layouts and signatures were written for
+ABI_VERSION = 660  # ssak_version() of the library this binding's struct layouts and signatures were written for
 
 
 class GemmDesc(C.Structure):
@@ -231,6 +231,14 @@ def _load():
         "ssak_debug_mel_to_cl": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
         "ssak_debug_add_rowvec": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
         "ssak_debug_copy_rows_padded": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+        "ssak_debug_specaug_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        "ssak_debug_specaug_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+        "ssak_debug_colsum": (i32, [vp, C.c_long, i32, i32, vp, vp, sz, vp, vp, i32, i32, vp]),
+        "ssak_debug_gelu_grad_mul": (i32, [vp, vp, vp, C.c_long, i32, vp]),
+        "ssak_debug_add": (i32, [vp, vp, vp, C.c_long, i32, vp]),
+        "ssak_debug_transpose_batched": (i32, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), vp]),
+        "ssak_debug_reduce": (i32, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_long), C.POINTER(i32), C.POINTER(i32), i32,
+                                     C.POINTER(i32), i32, C.POINTER(i32), C.POINTER(i32), vp]),
     }
     lib.ssak_version.restype = i32
     got = lib.ssak_version()
@@ -1261,3 +1269,56 @@ def debug_copy_rows_padded(src, dst):
     """``k_copy_rows_padded_t``: src [B, F, H] -> dst [B, RS, H], rows >= F zero."""
     B, F, H = src.shape
     check(lib.ssak_debug_copy_rows_padded(ptr(src), ptr(dst), B, F, dst.shape[1], H, _row_dtype(src), stream()))
+
+
+# ------------------------------------------------------------------ test-only: the engine's helper kernels (ABI 660).  Every
+# wrapper launches into the caller's buffers; ``scratch`` is an fp32 tensor (or None: the atomic path of the column sum).
+def debug_specaug_fwd(h, mask, flens, embed):
+    """``k_specaug_fwd_t`` in place on h [B, F, C] (bf16 or fp32): mask [B, F] uint8 or None, flens [B] int32 or None, embed [C] fp32."""
+    B, F, Cc = h.shape
+    check(lib.ssak_debug_specaug_fwd(ptr(h), ptr(mask), ptr(flens), ptr(embed), B, F, Cc, _row_dtype(h), stream()))
+
+
+def debug_specaug_bwd(dh, mask, flens, dembed, scratch=None, scratch_floats=None):
+    """``k_specaug_bwd_t`` in place on dh [B, F, C]; dembed [C] fp32 +=.  ``scratch_floats`` defaults to the scratch's size."""
+    B, F, Cc = dh.shape
+    nf = (0 if scratch is None else scratch.numel()) if scratch_floats is None else int(scratch_floats)
+    check(lib.ssak_debug_specaug_bwd(ptr(dh), ptr(mask), ptr(flens), ptr(dembed), B, F, Cc, _row_dtype(dh), ptr(scratch), nf, stream()))
+
+
+def debug_colsum(X, N: int, out, scratch=None, scratch_floats=None, rowmask=None, flens=None, F: int = 0):
+    """``k_colsum_t``: out [N] fp32 += the column sums of the first N columns of X [M, ld] (ld = X's row stride)."""
+    M, ld = X.shape
+    nf = (0 if scratch is None else scratch.numel()) if scratch_floats is None else int(scratch_floats)
+    check(lib.ssak_debug_colsum(ptr(X), ld, M, N, ptr(out), ptr(scratch), nf, ptr(rowmask), ptr(flens), int(F), _row_dtype(X), stream()))
+
+
+def debug_gelu_grad_mul(dy, pre, out, n: int):
+    """``k_gelu_grad_mul_t``: out[:n] = dy[:n] * gelu'(pre[:n]) (flat tensors of one storage type)."""
+    check(lib.ssak_debug_gelu_grad_mul(ptr(dy), ptr(pre), ptr(out), int(n), _row_dtype(dy), stream()))
+
+
+def debug_add(a, b, out, n: int):
+    """``k_add_t``: out[:n] = a[:n] + b[:n]."""
+    check(lib.ssak_debug_add(ptr(a), ptr(b), ptr(out), int(n), _row_dtype(a), stream()))
+
+
+def debug_transpose_batched(src_ptrs, dst_ptrs, R, Cs):
+    """``k_transpose_bf16_batched``: dst[i] [C, R] = src[i] [R, C]^T; device addresses (``data_ptr()``, any alignment) and shapes."""
+    n = len(src_ptrs)
+    assert len(dst_ptrs) == n and len(R) == n and len(Cs) == n
+    check(lib.ssak_debug_transpose_batched(n, (C.c_void_p * n)(*src_ptrs), (C.c_void_p * n)(*dst_ptrs), (C.c_int * n)(*R),
+                                           (C.c_int * n)(*Cs), stream()))
+
+
+def debug_reduce(jobs, call_sizes, use_sink: bool):
+    """``k_reduce`` on jobs = [(partial, out, stride, slots, ncols), ...] (fp32 tensors), issued as consecutive calls of
+    ``call_sizes`` jobs, under a local ReduceSink that is flushed at the end (``use_sink``) or directly.  Returns (jobs queued,
+    jobs run directly)."""
+    n, nc = len(jobs), len(call_sizes)
+    queued, direct = C.c_int(-1), C.c_int(-1)
+    check(lib.ssak_debug_reduce(n, (C.c_void_p * n)(*[j[0].data_ptr() for j in jobs]), (C.c_void_p * n)(*[j[1].data_ptr() for j in jobs]),
+                                (C.c_long * n)(*[int(j[2]) for j in jobs]), (C.c_int * n)(*[int(j[3]) for j in jobs]),
+                                (C.c_int * n)(*[int(j[4]) for j in jobs]), nc, (C.c_int * nc)(*[int(v) for v in call_sizes]),
+                                int(bool(use_sink)), C.byref(queued), C.byref(direct), stream()))
+    return queued.value, direct.value
