@@ -908,6 +908,39 @@ int ssak_layernorm_bwd(const void* g1, const void* g2, const void* r, const floa
                        const void* g_res, void* dr, float* dgamma, float* dbeta, int M, int C, int dtype, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- Whisper LoRA (additive to ABI 660: ssak_version() is unchanged): the adapter arithmetic around a frozen nn.Linear ----
+ * What peft's LoRA layer adds to the decoder's q_proj / v_proj (ssak/train/transformers/whisper_train.py:374-429; r = 32,
+ * lora_alpha = 64, lora_dropout = 0.05): y += s * dropout(x) A^T B^T with s = lora_alpha / r.  x [M, D_in] bf16 with row stride
+ * ldx; A [r, D_in] and B [D_out, r] contiguous (bf16 shadows of fp32 masters; ssak_lora_merge reads the masters); keep = the bits
+ * of dropout site `site` under `seed` at (row, col) of x (ssak_debug_dropout_mask(seed, site, drop_p, M, D_in) reproduces them;
+ * drop_p = 0: no mask), xd = keep * x / (1 - p) with the 16-bit threshold's realised p.  bf16 storage, fp32 accumulation, no
+ * atomics: two calls on the same inputs give the same bits.
+ *
+ * Contract of the four entries: r in {8, 16, 32, 64}; D_in, D_out multiples of 64 up to 1280 (ssak_lora_merge: up to 5120, the
+ * feed-forward width, for adapters merged at load); M >= 1, any remainder; row strides multiples of 8 and at least the widths;
+ * operands 16-byte aligned; D_in <= 16 384 with drop_p > 0.  Anything else, or a null operand other than the ones marked optional,
+ * is SSAK_ERR_INVALID before any launch.
+ *
+ * ssak_lora_fwd.  t [M, r] bf16 contiguous = bf16(xd A^T) (kept for the backward; NULL: not written); y[:, 0:D_out] (row stride ldy:
+ * a column block of a packed q|k|v or k|v output) = bf16(float(y) + s * t B^T), in place, the product reading the rounded t.
+ * ssak_lora_bwd_input.  dt [M, r] bf16 = bf16(s * dy B), dy a column block with row stride lddy; if dx is given (NULL: skipped):
+ * dx = bf16((accumulate ? float(dx) : 0) + keep * (dt A) / (1 - p)), row stride lddx.
+ * ssak_lora_bwd_weights.  dB [D_out, r] fp32 = s * dy^T t, dA [r, D_in] fp32 = dt^T xd (mask regenerated), both written.  The sum
+ * over M: first-stage partials over fixed 512-row ranges in `workspace` (>= ssak_lora_bwd_weights_workspace_bytes), added in
+ * ascending range order by a second stage.
+ * ssak_lora_merge.  w_out [D_out, D_in] bf16 = bf16(w_master + s * B A): fp32 masters, fp32 FMAs in ascending r; w_out_f32 (NULL:
+ * not written; may be w_master itself) receives the same value before the rounding to bf16. */
+int ssak_lora_fwd(const void* x, long ldx, const void* A, const void* B, void* y, long ldy, void* t, int M, int D_in, int D_out, int r,
+                  float scaling, uint64_t seed, uint32_t site, float drop_p, void* stream);
+int ssak_lora_bwd_input(const void* dy, long lddy, const void* A, const void* B, void* dt, void* dx, long lddx, int accumulate, int M, int D_in,
+                        int D_out, int r, float scaling, uint64_t seed, uint32_t site, float drop_p, void* stream);
+size_t ssak_lora_bwd_weights_workspace_bytes(int M, int D_in, int D_out, int r);
+int ssak_lora_bwd_weights(const void* dy, long lddy, const void* t, const void* dt, const void* x, long ldx, float* dB, float* dA, int M,
+                          int D_in, int D_out, int r, float scaling, uint64_t seed, uint32_t site, float drop_p, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int ssak_lora_merge(const float* w_master, const float* A, const float* B, void* w_out, float* w_out_f32, int D_in, int D_out, int r, float scaling,
+                    void* stream);
+
 /* ---- TEST-ONLY entries (not part of the product path; kept in the release library so that the parity tests run against the
  * library that ships): dropout bits of one site ------------------------------------------------------------------------
  * The engine stores no dropout mask: each site recomputes keep(seed, site, element) in its forward and backward kernels

@@ -201,6 +201,11 @@ def _load():
         "ssak_layernorm_fwd_stats": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]),
         "ssak_layernorm_bwd_workspace_bytes": (sz, [i32]),
         "ssak_layernorm_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+        "ssak_lora_fwd": (i32, [vp, C.c_long, vp, vp, vp, C.c_long, vp, i32, i32, i32, i32, f32, C.c_uint64, C.c_uint32, f32, vp]),
+        "ssak_lora_bwd_input": (i32, [vp, C.c_long, vp, vp, vp, vp, C.c_long, i32, i32, i32, i32, i32, f32, C.c_uint64, C.c_uint32, f32, vp]),
+        "ssak_lora_bwd_weights_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "ssak_lora_bwd_weights": (i32, [vp, C.c_long, vp, vp, vp, C.c_long, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, C.c_uint32, f32, vp, sz, vp]),
+        "ssak_lora_merge": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, vp]),
         "ssak_debug_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, C.c_long, i32, vp, C.POINTER(f32), vp]),
         "ssak_debug_attention_dropout_mask": (i32, [C.c_uint64, C.c_uint32, f32, i32, i32, i32, vp, vp]),
         "ssak_debug_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, C.c_uint64, C.c_uint32, f32, C.c_uint32,
@@ -1061,6 +1066,76 @@ def layernorm_bwd(g1, g2, r, mean, rstd, gamma, g_res, dr, dgamma, dbeta, worksp
     check(lib.ssak_layernorm_bwd(ptr(g1), ptr(g2), ptr(r), ptr(mean), ptr(rstd), ptr(gamma), ptr(g_res), ptr(dr), ptr(dgamma), ptr(dbeta), M, Cc,
                                  _row_dtype(r), ptr(ws), ws.numel(), stream()))
     return dr
+
+
+# ------------------------------------------------------------------ Whisper LoRA: the adapter around a frozen nn.Linear
+LORA_SITE_BASE = 4096  # dropout sites of the decoder's adapters: LORA_SITE_BASE + 4 * layer + which (the encoder engine's own
+#                        sites are 1 .. 3 and 16 + 4 * layer + 0 .. 3, the classification head's 4 and 5)
+
+
+def _lora_dims(A: torch.Tensor, B: torch.Tensor, dtype):
+    assert A.is_cuda and B.is_cuda and A.dtype == dtype and B.dtype == dtype and A.is_contiguous() and B.is_contiguous()
+    assert A.dim() == 2 and B.dim() == 2 and A.shape[0] == B.shape[1], "A [r, D_in] and B [D_out, r]"
+    return A.shape[0], A.shape[1], B.shape[0]
+
+
+def _rows_bf16(t: torch.Tensor, M: int, width: int, what: str):
+    assert t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1 and t.shape == (M, width), \
+        f"{what}: [{M}, {width}] bf16 (a column slice is fine), got {tuple(t.shape)} {t.dtype}"
+
+
+def lora_fwd(x, A, B, y, scaling: float, t=None, seed: int = 0, site: int = 0, drop_p: float = 0.0):
+    """``ssak_lora_fwd``: y [M, D_out] (a 2-D tensor or a column slice, updated in place) += scaling * bf16(dropout(x) A^T) B^T;
+    ``t`` [M, r] bf16 contiguous receives the rounded down-projection (None: not kept) -> y."""
+    r, D_in, D_out = _lora_dims(A, B, torch.bfloat16)
+    M = x.shape[0]
+    _rows_bf16(x, M, D_in, "x")
+    _rows_bf16(y, M, D_out, "y")
+    assert t is None or (t.dtype == torch.bfloat16 and t.is_contiguous() and t.shape == (M, r))
+    check(lib.ssak_lora_fwd(ptr(x), x.stride(0), ptr(A), ptr(B), ptr(y), y.stride(0), ptr(t), M, D_in, D_out, r, float(scaling),
+                            C.c_uint64(int(seed)), int(site), float(drop_p), stream()))
+    return y
+
+
+def lora_bwd_input(dy, A, B, dt, scaling: float, dx=None, accumulate: bool = False, seed: int = 0, site: int = 0, drop_p: float = 0.0):
+    """``ssak_lora_bwd_input``: dt [M, r] bf16 = scaling * dy B; with ``dx`` [M, D_in] (a tensor or a column slice):
+    dx (+)= keep * (dt A) / (1 - p) -> dt."""
+    r, D_in, D_out = _lora_dims(A, B, torch.bfloat16)
+    M = dy.shape[0]
+    _rows_bf16(dy, M, D_out, "dy")
+    assert dt.dtype == torch.bfloat16 and dt.is_contiguous() and dt.shape == (M, r)
+    if dx is not None:
+        _rows_bf16(dx, M, D_in, "dx")
+    check(lib.ssak_lora_bwd_input(ptr(dy), dy.stride(0), ptr(A), ptr(B), ptr(dt), ptr(dx), 0 if dx is None else dx.stride(0), int(bool(accumulate)),
+                                  M, D_in, D_out, r, float(scaling), C.c_uint64(int(seed)), int(site), float(drop_p), stream()))
+    return dt
+
+
+def lora_bwd_weights(dy, t, dt, x, dA, dB, scaling: float, seed: int = 0, site: int = 0, drop_p: float = 0.0, workspace=None):
+    """``ssak_lora_bwd_weights``: dB [D_out, r] fp32 = scaling * dy^T t, dA [r, D_in] fp32 = dt^T dropout(x) (both written; the mask
+    is regenerated from ``seed`` / ``site``)."""
+    assert dA.is_cuda and dB.is_cuda and dA.dtype == torch.float32 and dB.dtype == torch.float32 and dA.is_contiguous() and dB.is_contiguous()
+    assert dA.dim() == 2 and dB.dim() == 2 and dA.shape[0] == dB.shape[1], "dA [r, D_in] and dB [D_out, r]"
+    r, D_in, D_out = dA.shape[0], dA.shape[1], dB.shape[0]
+    M = x.shape[0]
+    _rows_bf16(x, M, D_in, "x")
+    _rows_bf16(dy, M, D_out, "dy")
+    for a in (t, dt):
+        assert a.dtype == torch.bfloat16 and a.is_contiguous() and a.shape == (M, r)
+    ws = workspace if workspace is not None else _ws(lib.ssak_lora_bwd_weights_workspace_bytes(M, D_in, D_out, r), x.device)
+    check(lib.ssak_lora_bwd_weights(ptr(dy), dy.stride(0), ptr(t), ptr(dt), ptr(x), x.stride(0), ptr(dB), ptr(dA), M, D_in, D_out, r,
+                                    float(scaling), C.c_uint64(int(seed)), int(site), float(drop_p), ptr(ws), ws.numel(), stream()))
+
+
+def lora_merge(w_master, A, B, w_out, scaling: float, w_out_f32=None):
+    """``ssak_lora_merge``: w_out [D_out, D_in] bf16 = bf16(w_master + scaling * B A) from the fp32 masters; ``w_out_f32`` (None, or
+    ``w_master`` itself) receives the value before the rounding -> w_out."""
+    r, D_in, D_out = _lora_dims(A, B, torch.float32)
+    assert w_master.is_cuda and w_master.dtype == torch.float32 and w_master.is_contiguous() and w_master.shape == (D_out, D_in)
+    assert w_out.is_cuda and w_out.dtype == torch.bfloat16 and w_out.is_contiguous() and w_out.shape == (D_out, D_in)
+    assert w_out_f32 is None or (w_out_f32.dtype == torch.float32 and w_out_f32.is_contiguous() and w_out_f32.shape == (D_out, D_in))
+    check(lib.ssak_lora_merge(ptr(w_master), ptr(A), ptr(B), ptr(w_out), ptr(w_out_f32), D_in, D_out, r, float(scaling), stream()))
+    return w_out
 
 
 # ------------------------------------------------------------------ test-only: the dropout bits of one site

@@ -1,10 +1,11 @@
-"""Full fine-tuning of a Whisper model on Kaldi folders, on one MI355X (the reference's ssak/train/transformers/whisper_train.py,
-its non-PEFT branch)::
+"""Fine-tuning of a Whisper model on Kaldi folders, on one MI355X (the reference's ssak/train/transformers/whisper_train.py): every
+parameter (its non-PEFT branch) or, with ``--lora``, the reference's LoRA adapters on the bf16 base::
 
     python -m ssak_amd.train_whisper TRAIN VALID --base_model DIR [--lang fr] [--task transcribe] [--batch_size 8] [--batch_size_eval N]
                                      [--learning_rate 1e-5] [--weight_decay 0.01] [--warmup_steps N] [--num_epochs 3] [--max_steps N]
                                      [--seed 42] [--max_duration 30] [--min_duration 0.1] [--max_text_length 448] [--eval_steps N]
                                      [--disable_first_eval] [-o OUTPUT_DIR] [--overwrite_output_dir] [--freeze_encoder]
+                                     [--lora [--lora_r 32] [--lora_alpha 64] [--lora_dropout 0.05]]
 
 ``TRAIN`` / ``VALID``: a Kaldi folder, several separated by commas, or a list file (:mod:`ssak_amd.data`).  ``DIR`` is a
 ``WhisperForConditionalGeneration`` folder in the HuggingFace layout WITH its tokenizer files (nothing is downloaded): labels are
@@ -14,10 +15,13 @@ through the device log-mel (:meth:`WhisperSeq2Seq.features`), the step is :meth:
 the steps by default -- and decay).  Every ``--eval_steps`` steps (default: every epoch), and before the first step unless
 ``--disable_first_eval``, validation reports ``eval_loss`` (teacher-forced) and the WER of :meth:`WhisperSeq2Seq.generate`
 (:func:`ssak_amd.metrics.text_wer`), and a checkpoint is written (``save_pretrained``: a folder ``from_pretrained`` and transformers
-read).
+read).  ``--lora``: adapters on the decoder's ``q_proj`` / ``v_proj`` (:meth:`WhisperSeq2Seq.add_lora`), the base frozen; the checkpoints
+are PEFT adapter folders (``checkpoint-<step>/adapter_model/``, and ``adapter_config.json`` + ``adapter_model.safetensors`` with the
+tokenizer files in the output folder), which ``from_pretrained`` -- and so ``python -m ssak_amd.whisper_infer`` -- loads merged.
 
 Differences from the reference, each refused by name where it is asked for: ``--gradient_accumulation_steps`` defaults to 1 here
-(16 there) and no other value is built; ``--peft``, ``--int4``, ``--data_augmentation`` and ``--text_augmentation`` are not built.
+(16 there) and no other value is built; ``--peft`` (int8 + LoRA), ``--int4``, ``--data_augmentation`` and ``--text_augmentation`` are not
+built.
 One GPU; no data parallelism.
 
 :func:`run_training` is the loop itself: it takes utterances, a ``tokenize`` callable (text -> label ids) and, for the WER, a
@@ -26,16 +30,18 @@ One GPU; no data parallelism.
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import math
 import os
+import shutil
 import sys
 import time
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 
-_NOT_BUILT = {"peft": "--peft: LoRA / int8 training is not built (full fine-tuning only)",
+_NOT_BUILT = {"peft": "--peft: the reference's int8 + LoRA branch is not built; `--lora` trains the same adapters on the bf16 base",
               "int4": "--int4: 4-bit quantisation is not built",
               "data_augmentation": "--data_augmentation: audio augmentation is not wired into Whisper fine-tuning (python -m ssak_amd.train "
                                    "--data_augment has it for wav2vec2)",
@@ -66,6 +72,10 @@ def parse_args(argv=None):
     ap.add_argument("-o", "--output_dir", default=".", help="parent folder of the output folder")
     ap.add_argument("--overwrite_output_dir", action="store_true")
     ap.add_argument("--freeze_encoder", action="store_true", help="train the decoder only")
+    ap.add_argument("--lora", action="store_true", help="train LoRA adapters on the decoder's q_proj / v_proj (bf16 base, everything else frozen)")
+    ap.add_argument("--lora_r", type=int, default=32)
+    ap.add_argument("--lora_alpha", type=float, default=64)
+    ap.add_argument("--lora_dropout", type=float, default=0.05)
     ap.add_argument("--device", default="cuda:0")
     for flag in _NOT_BUILT:
         ap.add_argument("--" + flag, action="store_true", help=argparse.SUPPRESS)
@@ -78,6 +88,8 @@ def parse_args(argv=None):
                  f"(the default here is 1, the reference's is 16: raise --batch_size instead)")
     if args.batch_size < 1 or (args.batch_size_eval is not None and args.batch_size_eval < 1):
         ap.error("--batch_size and --batch_size_eval must be at least 1")
+    if args.lora_r not in (8, 16, 32, 64) or not 0.0 <= args.lora_dropout < 1.0:
+        ap.error("--lora_r must be 8, 16, 32 or 64 and --lora_dropout in [0, 1)")
     if args.max_text_length < 1 or args.num_epochs < 1:
         ap.error("--max_text_length and --num_epochs must be at least 1")
     args.batch_size_eval = args.batch_size_eval or args.batch_size
@@ -113,7 +125,8 @@ def evaluate(model, utts, labels, batch_size: int, detokenize=None, language=Non
         total += float(model.forward_train(enc, padded, keep_graph=False).item()) * n
         n_tok += n
         if detokenize is not None:
-            res = model.generate(enc, language=language, task=task)
+            with model.lora_merged() if model._lora is not None else contextlib.nullcontext():
+                res = model.generate(enc, language=language, task=task)
             refs += [x.text for x in u]
             hyps += [detokenize(t) for t in res.tokens]
     out = {"eval_loss": total / max(n_tok, 1), "eval_tokens": n_tok}
@@ -124,11 +137,15 @@ def evaluate(model, utts, labels, batch_size: int, detokenize=None, language=Non
 
 def run_training(model, train_utts, valid_utts, tokenize, *, batch_size=8, batch_size_eval=None, learning_rate=1e-5, weight_decay=0.01,
                  warmup_steps=None, num_epochs=3, max_steps=None, seed=42, max_text_length=448, eval_steps=None, disable_first_eval=False,
-                 output_dir=None, detokenize=None, language=None, task="transcribe", log=None) -> List[dict]:
+                 output_dir=None, detokenize=None, language=None, task="transcribe", log=None, lora: Optional[dict] = None) -> List[dict]:
     """The training loop -> the log records (dicts; ``log`` is called with each).  Utterances whose labels exceed
     ``max_text_length`` tokens are dropped, as the reference's filter does.  With ``output_dir`` a checkpoint
-    ``checkpoint-<step>`` is written at every validation and the final model into ``output_dir`` itself."""
-    from .whisper_train import TRAIN_ROW_CHUNK, WhisperAdamW
+    ``checkpoint-<step>`` is written at every validation and the final model into ``output_dir`` itself.  ``lora`` (the arguments
+    of :meth:`WhisperSeq2Seq.add_lora`; {} for the reference's): the adapters are trained on the frozen base and the checkpoints are
+    adapter folders, ``checkpoint-<step>/adapter_model/`` and, in ``output_dir``, the adapter next to the tokenizer files."""
+    from .whisper_train import _TOKENIZER_FILES, TRAIN_ROW_CHUNK, WhisperAdamW
+    if lora is not None and model._lora is None:
+        model.add_lora(**dict({"seed": seed}, **lora))
     model.row_chunk = max(model.row_chunk, TRAIN_ROW_CHUNK)
     log = log or (lambda rec: print(json.dumps(rec), flush=True))
     start = model.config.decoder_start_token_id
@@ -159,7 +176,8 @@ def run_training(model, train_utts, valid_utts, tokenize, *, batch_size=8, batch
         if valid_utts:
             rec.update(evaluate(model, valid_utts, valid_labels, batch_size_eval or batch_size, detokenize, language, task))
         if output_dir is not None:
-            rec["checkpoint"] = model.save_pretrained(os.path.join(output_dir, f"checkpoint-{step}"))
+            ckpt = os.path.join(output_dir, f"checkpoint-{step}")
+            rec["checkpoint"] = model.save_pretrained(ckpt) if lora is None else model.save_adapter(os.path.join(ckpt, "adapter_model"))
         emit(rec)
 
     if not disable_first_eval and valid_utts:
@@ -184,8 +202,14 @@ def run_training(model, train_utts, valid_utts, tokenize, *, batch_size=8, batch
                 break
         if step == total:
             break
-    if output_dir is not None:
+    if output_dir is not None and lora is None:
         model.save_pretrained(output_dir)
+    elif output_dir is not None:
+        model.save_adapter(output_dir)
+        src = model.name_or_path
+        for name in _TOKENIZER_FILES if src is not None and os.path.abspath(src) != os.path.abspath(output_dir) else ():
+            if os.path.isfile(os.path.join(src, name)):
+                shutil.copyfile(os.path.join(src, name), os.path.join(output_dir, name))
     return records
 
 
@@ -213,7 +237,8 @@ def main(argv=None):
                  learning_rate=args.learning_rate, weight_decay=args.weight_decay, warmup_steps=args.warmup_steps, num_epochs=args.num_epochs,
                  max_steps=args.max_steps, seed=args.seed, max_text_length=args.max_text_length, eval_steps=args.eval_steps,
                  disable_first_eval=args.disable_first_eval, output_dir=out, detokenize=lambda ids: tok.decode(ids, skip_special_tokens=True).strip(),
-                 language=args.lang, task=args.task)
+                 language=args.lang, task=args.task,
+                 lora=dict(r=args.lora_r, alpha=args.lora_alpha, dropout=args.lora_dropout) if args.lora else None)
 
 
 if __name__ == "__main__":

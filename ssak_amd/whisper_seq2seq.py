@@ -34,7 +34,7 @@ masters with a bf16 shadow; activations bf16, logits fp32.  Its structure:
   :func:`beam_rank`.
 
 Not built: a beam ``patience``, ``condition_on_previous_text`` / ``initial_prompt``, word timestamps, a skinny-M GEMM for the token
-step, hipGraph capture of the step, LoRA, an fp32-exact mode of the decoder.  Timing: tools/bench_whisper_decoder.py,
+step, hipGraph capture of the step, an fp32-exact mode of the decoder.  LoRA adapters: ssak_amd/whisper_lora.py.  Timing: tools/bench_whisper_decoder.py,
 tools/bench_whisper_generate.py, tools/bench_whisper_transcribe.py, tools/bench_whisper_beam.py, tools/bench_whisper_sample.py,
 tools/bench_whisper_train.py; DESIGN.md has a section for each ("Whisper decoder", "Whisper generation", "Whisper long-form
 transcription", "Whisper beam search", "Whisper sampling and temperature fallback", "Whisper fine-tuning").
@@ -52,6 +52,7 @@ import torch
 
 from . import hip
 from .whisper import WhisperCTCConfig, WhisperEncoderForCTC
+from .whisper_lora import WhisperLoraMixin, find_adapter_config, load_adapter_folder
 from .whisper_train import WhisperTrainMixin
 
 ROW_CHUNK = 256  # rows of the vocabulary projection in flight (51 865 columns: 53 MB of fp32 logits)
@@ -331,7 +332,7 @@ def _decoder_layout(cfg: WhisperSeq2SeqConfig):
     return layout, off
 
 
-class WhisperSeq2Seq(WhisperTrainMixin):
+class WhisperSeq2Seq(WhisperTrainMixin, WhisperLoraMixin):
     """``WhisperSeq2Seq.from_pretrained(folder)``; :meth:`encode`, :meth:`decode_logprobs`, :meth:`score`, :meth:`detect_language`,
     :meth:`generate`, :meth:`transcribe`; training: :meth:`forward_train`, :meth:`backward`, :meth:`save_pretrained`
     (ssak_amd/whisper_train.py).  The module docstring names the parts."""
@@ -398,10 +399,15 @@ class WhisperSeq2Seq(WhisperTrainMixin):
         ``generation_config.json`` for ``lang_to_id`` and ``decoder_start_token_id`` (else the ``<|xx|>`` entries of
         ``added_tokens.json`` / ``vocab.json``) and for what :meth:`generate` needs: ``eos_token_id``, ``pad_token_id``,
         ``suppress_tokens``, ``begin_suppress_tokens``, ``task_to_id``, ``no_timestamps_token_id``.  Unsupported configurations are
-        refused by name."""
+        refused by name.  A PEFT folder (an ``adapter_config.json`` in it or below it, as the reference's inference looks for one) loads
+        the base model its ``base_model_name_or_path`` names, a local folder, and merges the LoRA adapter into it
+        (ssak_amd/whisper_lora.py)."""
         from .checkpoint import load_state_dict_file
         if not os.path.isdir(folder):
             raise FileNotFoundError(f"{folder}: not a model folder (nothing is downloaded: pass a local folder in the HuggingFace layout)")
+        adapter_dir = find_adapter_config(folder)
+        if adapter_dir is not None:
+            return load_adapter_folder(cls, folder, adapter_dir, device, freeze_encoder)
         with open(os.path.join(folder, "config.json")) as f:
             d = json.load(f)
         extra = {}
@@ -493,6 +499,9 @@ class WhisperSeq2Seq(WhisperTrainMixin):
             raise ValueError(f"{tokens.shape[0]} token sequences for {B} encoder outputs")
         L, nh = tokens.shape[1], cfg.decoder_attention_heads
         enc2 = enc.reshape(B * S, D)
+        lora = self._lora_active()  # unmerged adapters: their products follow the base q_proj / v_proj products
+        if lora and cross_kv is not None:
+            raise RuntimeError("a generation's cross k|v buffer holds no adapter: generate() runs on the merged shadow (lora_merged())")
         bf = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=self.device)
         f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
@@ -529,6 +538,9 @@ class WhisperSeq2Seq(WhisperTrainMixin):
                 s = {"ln1": ln}  # (the layer's buffers live in ``s`` alone: without ``keep`` they go when the next layer starts)
                 # causal self-attention: q | k | v in one product, the attention reads its three column blocks in place
                 s["qkv"] = self._linear(ln[1], self._w(p + "self_attn.q_proj.weight", 3), self._f(p + "self_attn.q_proj.bias", 3))
+                if lora:
+                    self._lora_fwd(l, "self_attn", "q_proj", ln[1], s["qkv"][:, :D], s)
+                    self._lora_fwd(l, "self_attn", "v_proj", ln[1], s["qkv"][:, 2 * D:], s)
                 if self_cache is not None:
                     self_cache[l, :, :L].copy_(s["qkv"][:, D:].view(B, L, 2 * D))
                 s["ctx_s"], s["lse_s"] = attend(s["qkv"][:, :D], s["qkv"][:, D:2 * D], s["qkv"][:, 2 * D:], L, causal=True)
@@ -538,6 +550,9 @@ class WhisperSeq2Seq(WhisperTrainMixin):
                 s["q_c"] = self._linear(ln[1], self._w(p + "encoder_attn.q_proj.weight"), self._f(p + "encoder_attn.q_proj.bias"))
                 s["kv_c"] = cross_kv[l] if cross_kv is not None else self._linear(enc2, self._w(p + "encoder_attn.k_proj.weight", 2),
                                                                                   self._f(p + "encoder_attn.k_proj.bias", 2))
+                if lora:
+                    self._lora_fwd(l, "encoder_attn", "q_proj", ln[1], s["q_c"], s)
+                    self._lora_fwd(l, "encoder_attn", "v_proj", enc2, s["kv_c"][:, D:], s)
                 s["ctx_c"], s["lse_c"] = attend(s["q_c"], s["kv_c"][:, :D], s["kv_c"][:, D:], S, klens=enc_lens)
                 y = self._linear(s["ctx_c"], self._w(p + "encoder_attn.out_proj.weight"), self._f(p + "encoder_attn.out_proj.bias"))
                 s["ln3"] = ln = norm(y, ln[0], p + "final_layer_norm")
@@ -992,6 +1007,12 @@ class WhisperSeq2Seq(WhisperTrainMixin):
         ``GenerateResult.samples`` lists them all.  The same ``seed`` gives the same result.  ``beam_size`` together with
         ``temperature > 0`` is refused (whisper drops the beam there; :func:`ssak_amd.whisper_transcribe.transcribe` does the
         dropping).  ``temperature = 0`` (the default) leaves the call as it was and ignores ``best_of`` and ``seed``."""
+        if self._lora_active():  # the token step and the cross k|v buffer read the shadow: merge the adapters for the call
+            with self.lora_merged():
+                return self.generate(enc_or_audio, prompt=prompt, language=language, task=task, max_new_tokens=max_new_tokens, enc_lens=enc_lens,
+                                     suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, eos_token_id=eos_token_id,
+                                     poll_every=poll_every, timestamps=timestamps, beam_size=beam_size, length_penalty=length_penalty,
+                                     temperature=temperature, best_of=best_of, seed=seed)
         enc = self._as_enc(enc_or_audio)
         B, V = enc.shape[0], self.config.vocab_size
         pl = self._gen_plan(B, prompt, language, task, max_new_tokens, suppress_tokens, begin_suppress_tokens, eos_token_id, poll_every,

@@ -11,7 +11,8 @@ operands K-major, ``accumulate`` and a library-sized split; the GELU pair of fc1
 Every sum has a fixed order: two steps from the same state give the same bits.
 
 Not built: decoder dropout / layerdrop (refused by name; every published Whisper config has them at
-0), gradient checkpointing, gradient accumulation, LoRA / int8 / int4, data parallelism.
+0), gradient checkpointing, gradient accumulation, int8 / int4 quantisation of the base, data parallelism.  LoRA on the bf16 base:
+ssak_amd/whisper_lora.py (``add_lora``; ``backward`` and :class:`WhisperAdamW` then take their frozen-base branches).
 """
 from __future__ import annotations
 
@@ -130,14 +131,24 @@ class WhisperTrainMixin:
         lens_host = self._enc_lens(enc_lens, B, S)
 
         layers = []  # (validation runs the keeping entries too and drops what they kept)
-        ln_f = self._decoder_hidden(enc, ids, lens_host, keep=layers)
+        lora_train = keep_graph and self._lora_active()  # adapters: dropout under this step's seed, each t kept
+        if keep_graph and self._lora is not None and self._lora_merged:
+            raise RuntimeError("forward_train(): the adapters are merged into the shadow; unmerge_lora() before a train step")
+        if lora_train:
+            self.lora_step += 1
+        self._lora_train_pass = lora_train
+        try:
+            ln_f = self._decoder_hidden(enc, ids, lens_host, keep=layers)
+        finally:
+            self._lora_train_pass = False
         targets = np.ascontiguousarray(lab.reshape(-1), dtype=np.int32)
         with torch.cuda.device(self.device):
             parts = [hip.token_logprobs(logits, cfg.vocab_size, targets[r0:r0 + n])[1] for r0, n, logits in self._project_chunks(ln_f[1])]
             lp = parts[0] if len(parts) == 1 else torch.cat(parts)
             loss = -(lp.sum(dtype=torch.float32) / n_scored).reshape(1)
         self._train = None if not keep_graph else dict(B=B, L=L, S=S, enc2=enc.reshape(B * S, D), enc_lens=lens_host, ids=ids, targets=targets,
-                                                       n_scored=n_scored, layers=layers, ln_f=ln_f, train_encoder=train_encoder)
+                                                       n_scored=n_scored, layers=layers, ln_f=ln_f, train_encoder=train_encoder,
+                                                       lora_seed=self.lora_drop_seed if lora_train else None)
         return loss
 
     # ------------------------------------------------------------------ backward
@@ -177,11 +188,14 @@ class WhisperTrainMixin:
     def backward(self, grad_scale: float = 1.0):
         """d (grad_scale * loss) / d parameters of the last :meth:`forward_train`: the decoder's into ``dec_grads`` (overwritten), the
         encoder's into ``encoder.grads`` (unless the forward was given an encoder output or ``freeze_encoder`` is set).  Returns
-        ``d_enc`` [B, S, D] fp32, the gradient of the encoder output."""
+        ``d_enc`` [B, S, D] fp32, the gradient of the encoder output.  With LoRA adapters (``add_lora``) the base is frozen: the
+        adapters' gradients go into ``lora_grads``, ``dec_grads`` is never allocated and None is returned."""
         s = self._train
         if s is None:
             raise RuntimeError("backward() needs a forward_train()")
         self._train = None
+        if self._lora is not None:  # frozen base: ssak_amd/whisper_lora.py
+            return self._backward_lora(s, grad_scale)
         cfg = self.config
         B, L, S, enc2 = s["B"], s["L"], s["S"], s["enc2"]
         D, nh, N, V = cfg.d_model, cfg.decoder_attention_heads, B * L, cfg.vocab_size
@@ -304,9 +318,16 @@ class WhisperAdamW:
         self.train_encoder = not model.freeze_encoder
         # (buffer of parameters, of gradients, of the shadow, count, ranges) per half
         self.halves = []
-        if self.train_encoder:
-            self.halves.append((enc.params, enc.grads, enc.shadow, enc.num_trainable, decay_ranges(enc)))
-        self.halves.append((model.dec_params, model.dec_grads, model.dec_shadow, model.dec_params.numel(), decoder_decay_ranges(model)))
+        if getattr(model, "_lora", None) is not None:
+            # adapters: the one half; HF's rule decays every LoRA weight (no name holds "bias" or a LayerNorm), the clip norm runs
+            # over the adapter gradients alone and the base gets neither moments nor a gradient buffer
+            self.train_encoder = False
+            n = model.lora_params.numel()
+            self.halves.append((model.lora_params, model.lora_grads, model.lora_shadow, n, [(0, n, True)]))
+        else:
+            if self.train_encoder:
+                self.halves.append((enc.params, enc.grads, enc.shadow, enc.num_trainable, decay_ranges(enc)))
+            self.halves.append((model.dec_params, model.dec_grads, model.dec_shadow, model.dec_params.numel(), decoder_decay_ranges(model)))
         self.exp_avg = [torch.zeros(n, dtype=torch.float32, device=dev) for _, _, _, n, _ in self.halves]
         self.exp_avg_sq = [torch.zeros(n, dtype=torch.float32, device=dev) for _, _, _, n, _ in self.halves]
         self.gnorm_sq = torch.zeros(1, dtype=torch.float32, device=dev)
